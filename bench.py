@@ -4,9 +4,16 @@
 One "step" = Model.forward + backward + AMSGrad (+ gradient all-reduce for N > 1) over one batch of
 B=32 synthetic MIND-shaped impressions per GPU (run.py:178-195), 4-layer student + 4-teacher KD.
 Inputs (token table, teacher tables, pre-drawn impression indices) are resident in HBM before the
-timed region.  Prints ONE JSON line on rank 0 (contract in the task statement).
+timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline; everything else the benchmark measures (roofline
+and step breakdown, box calibration launches, de-duplication loops, the other 16-bit type, the larger batch, the other
+BASELINE configurations, the CPU baseline, the data-parallel preflight / tail figures) runs with --full only.
+--dump-outputs DIR writes what the last timed step computed (losses, student scores, a fixed sample of the updated
+parameters) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 
   python bench.py --gpus 1 --steps 200 --warmup 20      (the defaults: SURVEY 8-d)
+  python bench.py --gpus 1 --steps 200 --warmup 20 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
 """
@@ -181,6 +188,24 @@ class BoxProbe:
         return {"calibration_launches": out}
 
 
+PARAM_SAMPLE = 1 << 20      # --dump-outputs: trainable parameters written (fixed, seeded positions; all of them if fewer)
+
+
+def dump_outputs(path, step_out, eng):
+    """What a caller of the timed step receives from its last step: the forward's losses [distill, target, emb, -] and
+    student_score (B, C), and the trainable fp32 parameters after the update (a fixed sample of PARAM_SAMPLE positions in
+    ascending order, drawn from a seeded generator).  float32 .npy files, a few MB in all."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    flat = eng.flat[True]
+    n = flat.numel()
+    pos = np.arange(n) if n <= PARAM_SAMPLE else np.sort(np.random.default_rng(0).choice(n, PARAM_SAMPLE, replace=False))
+    arrays = {"losses": step_out["losses"], "student_score": step_out["student_score"],
+              "params_sample": flat[torch.from_numpy(pos).to(flat.device)]}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def self_launch(a):
     """`python bench.py --gpus N` without a launcher: start N workers (one per GPU) under torch.distributed.run as a CHILD
     process and pass its exit code on.  Nothing in this process has touched the GPU yet (no HIP call, no
@@ -227,9 +252,10 @@ def main():
     ap.add_argument("--dp-sweep", action="store_true",
                     help="data-parallel runs only: after the headline also time {wgrad units 1, 2} x {5, 3 buckets} x {allreduce, rs_ag} "
                          "(30 steps each) and report them in the dp object")
-    ap.add_argument("--dedup", choices=["off", "also", "only"], default="also",
+    ap.add_argument("--dedup", choices=["off", "also", "only"], default=None,
                     help="in-batch news de-duplication (dedup.py): 'also' times it in a second loop and reports it beside "
-                         "the headline (which stays un-deduplicated), 'only' makes it the headline")
+                         "the headline (which stays un-deduplicated), 'only' makes it the headline (default: 'also' with --full, "
+                         "else 'off')")
     ap.add_argument("--frozen-cache", action="store_true",
                     help="with --dedup only: also take the frozen lower layers from the per-news cache in the headline loop "
                          "(run.py's default mode; not the BASELINE workload, which recomputes every layer)")
@@ -244,7 +270,20 @@ def main():
     ap.add_argument("--concat-batches", action="store_true",
                     help="tests only: the ranks' batches of a step are consecutive slices of ONE batch of world x B impressions drawn from "
                          "a common seed (so that a one-rank run with --batch world x B sees the concatenation); default: per-rank seeds")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline also run every other measurement (roofline + step breakdown + box, de-duplication "
+                         "loops, other dtype, larger batch, other configurations, CPU baseline, data-parallel preflight / tail); the "
+                         "--no-* options above leave single ones out.  Without it a run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (losses, student_score, a fixed sample of the "
+                         "updated trainable parameters) as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dedup is None:
+        a.dedup = "also" if a.full else "off"
+    if not a.full:
+        a.no_kernel_timing = a.no_other_dtype = a.no_larger_batch = a.no_configs = a.no_cpu_baseline = True
     # tests only (tests/test_dropin_gpu.py): TNR_BENCH_BACKEND=gloo runs the world > 1 path - self_launch, per-rank batches, bucketed
     # all-reduce with its waits, max over ranks, the dp object, --dp-sweep - as N processes over gloo, TNR_BENCH_SHARE_GPU=1 puts them
     # all on GPU 0, TNR_BENCH_DUMP_PARAMS=<file.npy> saves a sample of the trained parameters.  No throughput claim comes from it.
@@ -315,10 +354,12 @@ def main():
         eng.load_state_dict(init_sd)                 # same start; also drops the frozen-layer cache
         eng.adam_m.zero_(); eng.adam_v.zero_(); eng.adam_vmax.zero_(); eng.step_count = 0
 
+    step_out = {}                                    # what the latest step's forward returned (--dump-outputs)
+
     def one_step(eng, gs, i, use_plan):
         s = slice(i * B, (i + 1) * B)
-        eng.forward_indexed(comb, hidx[s], mask[s], cidx[s], label[s], tables if a.teachers else None,
-                            plans[i] if use_plan else None)
+        step_out["losses"], step_out["student_score"] = eng.forward_indexed(comb, hidx[s], mask[s], cidx[s], label[s],
+                                                                            tables if a.teachers else None, plans[i] if use_plan else None)
         eng.backward(after_bucket=gs.launch if use_dp else None)
         eng.step(lr=1e-4, grad_scale=gs.scale, sync=gs)      # per bucket: wait for its all-reduce, then its AMSGrad slice
 
@@ -332,9 +373,10 @@ def main():
     # what each leg's parity test allows and what it measured (tools/parity_measured.py runs the tests and writes the file; the
     # allowances beyond 1e-3 are measured ones)
     PARITY = {}
-    import glob as _glob
-    for pj in sorted(_glob.glob(os.path.join(ROOT, "profiles", "r*_parity_measured.json")), reverse=True)[:1]:
-        PARITY = json.load(open(pj))
+    if a.full or a.leg:
+        import glob as _glob
+        for pj in sorted(_glob.glob(os.path.join(ROOT, "profiles", "r*_parity_measured.json")), reverse=True)[:1]:
+            PARITY = json.load(open(pj))
 
     def stage2_leg(key, nl, tr, T_, dtype, what, W2=3, K2=20):
         try:
@@ -506,6 +548,8 @@ def main():
     # headline: W untimed warm-up steps, then exactly K timed steps, every NT GEMM launch bracketed by HIP events on its stream
     TKEY = "tnr_gemm_nt_ex_f16" if a.dtype == "fp16" else "tnr_gemm_nt_ex"
     dt = timed_loop(eng, gs, a.dedup == "only", None if a.no_kernel_timing else TKEY)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_out, eng)
     rec = timed_rec or None
     box = breakdown = None
     if not a.no_kernel_timing:
@@ -559,7 +603,7 @@ def main():
         # what stays serial behind the LAST collective on the fp16 path (the per-bucket scans of the earlier buckets hide under
         # the collectives still in flight): 8 more steps with the guard kernels and the update bracketed by events
         tail = None
-        if eng.scaler.enabled:
+        if a.full and eng.scaler.enabled:
             names = ("tnr_grad_nonfinite_scan", "tnr_grad_nonfinite_commit", "tnr_amsgrad_step_guarded")
             recs = {n_: [] for n_ in names}
             T.TIMED.update(recs)
@@ -591,7 +635,7 @@ def main():
                    "note": "all-reduce(sum) of fp32 gradients, 1/world folded into AMSGrad; every bucket but the last is launched "
                            "while backward still runs"}
     loss = float(eng.total_loss().item())
-    if use_dp and world == 1 and not any(kv.startswith("cus=") for kv in a.gemm_opt):
+    if a.full and use_dp and world == 1 and not any(kv.startswith("cus=") for kv in a.gemm_opt):
         # world-1 preflight for the first multi-GPU lease: what it costs THIS step to size the persistent GEMM grids for 248 / 240
         # of the 256 CUs (the CUs RCCL's kernels would get), 5 + 30 steps each, interleaved with the full-chip setting
         K_, W_ = K, W
@@ -739,9 +783,10 @@ def main():
                                "algorithmic_flops_per_launch": fl / len(rec)}
         else:
             out["roofline"] = None
-        out["parity"] = PARITY.get("headline")       # what the headline model's parity test allows and measured (tools/parity_measured.py):
-        #                                              B = 2 golden + `b32` (the benchmark's own batch) + `trajectory` (50 reference steps)
-        out["quality"] = PARITY.get("quality")       # tests/test_quality_gpu.py: AUC / MRR / nDCG against the reference-trained golden
+        if a.full:
+            out["parity"] = PARITY.get("headline")   # what the headline model's parity test allows and measured (tools/parity_measured.py):
+            #                                          B = 2 golden + `b32` (the benchmark's own batch) + `trajectory` (50 reference steps)
+            out["quality"] = PARITY.get("quality")   # tests/test_quality_gpu.py: AUC / MRR / nDCG against the reference-trained golden
         if box is not None:
             out["box"] = box
             cal = box["calibration_launches"]["mfma_heavy"]["us"]

@@ -79,7 +79,7 @@ def test_bench_dp_path_under_torchrun_single_rank():
     process group, the flat broadcast and the overlapped bucketed all-reduce + scaled AMSGrad all execute."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--force-dp", "--dp-sweep", "--no-configs"]
+           "--no-cpu-baseline", "--force-dp", "--dp-sweep", "--no-configs", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -118,7 +118,7 @@ def test_bench_two_ranks_over_gloo_match_one_rank_on_the_concatenated_batch(tmp_
         env = dict(os.environ, TNR_BENCH_BACKEND="gloo", TNR_BENCH_SHARE_GPU="1", TNR_BENCH_DUMP_PARAMS=dump)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--batch", str(batch), "--steps", str(steps),
                "--warmup", str(warm), "--concat-batches", "--no-cpu-baseline", "--no-configs", "--no-larger-batch", "--no-other-dtype",
-               "--dedup", "off", "--no-kernel-timing"] + (["--dp-sweep"] if gpus == 2 else [])
+               "--dedup", "off", "--no-kernel-timing", "--full"] + (["--dp-sweep"] if gpus == 2 else [])
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
         assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -145,6 +145,35 @@ def test_bench_two_ranks_over_gloo_match_one_rank_on_the_concatenated_batch(tmp_
     n_upd = steps + warm
     print("bench, 2 ranks (gloo) vs 1 rank: |param diff| mean %.2e max %.2e after %d steps at lr %g" % (diff.mean(), diff.max(), n_upd, lr))
     assert diff.mean() < 0.02 * lr and diff.max() <= 2.05 * lr * n_upd
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` times the headline alone (everything else behind --full) and --dump-outputs
+    writes what the last timed step computed; two runs with the same arguments see the same inputs and write the same arrays."""
+    import engine as E
+    runs = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["metric"] == "training impressions/sec" and d["unit"] == "impressions/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "fp16" and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+        assert not {"cpu_baseline", "configs", "other_dtype", "larger_batch", "dedup", "box", "step_breakdown_ms"} & set(d)
+        assert d["roofline"] is None
+        arrs = {f[:-4]: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))}
+        assert set(arrs) == {"losses", "student_score", "params_sample"}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in arrs.values())
+        assert arrs["student_score"].shape == (32, 5) and arrs["params_sample"].shape == (1 << 20,)
+        runs.append((d, arrs))
+    cfg = E.EngineConfig(n_layers=4, trainable_layers=(2, 3), num_teachers=4)
+    l = runs[0][1]["losses"].astype(np.float64)
+    assert abs(l[0] + cfg.coef * l[1] + l[2] - runs[0][0]["config"]["final_loss"]) < 1e-4
+    for k, v in runs[0][1].items():
+        assert np.array_equal(v, runs[1][1][k]), k
 
 
 def test_construction_time_init_and_pretrained_import(tmp_path):
