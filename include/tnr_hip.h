@@ -13,8 +13,9 @@
  *     returns a thread-local message; no C++ exception crosses the boundary;
  *   - the library never calls hipSetDevice / hipDeviceSynchronize / hipStreamSynchronize: the caller's current device
  *     rules and nothing ever blocks the host;
- *   - device state kept by the library: ONE thing, the tile-queue counters of the persistent GEMM (see
- *     tnr_gemm_queue_reset below); everything else lives in caller-owned buffers;
+ *   - device state kept by the library: ONE thing, the tile-queue counters of the persistent GEMMs (see
+ *     tnr_gemm_queue_reset below); host state: the process-wide GEMM option block (tnr_gemm_set_option), the buffer pointer
+ *     of tnr_gemm_clock_stamps and the run-time binding of RCCL (tnr_comm_*); everything else lives in caller-owned buffers;
  *   - 16-bit activations are bf16 (TNR_BF16); "ld" arguments are row strides in
  *     ELEMENTS; row-major everywhere.
  */
@@ -61,11 +62,9 @@ typedef struct tnr_dropout {
 int tnr_version(void);
 const char* tnr_last_error(void);
 
-/* Collectives are NOT part of this ABI: the gradient average of the reference (hvd.DistributedOptimizer / hvd.allreduce,
- * Tiny-NewsRec/run.py:141-149, utils.py:43-60) is done by the caller with torch.distributed (backend "nccl" = RCCL) on the
- * flat gradient buffer (tiny-newsrec_amd/dist.py); every entry point here is a single-device operation on the stream passed
- * last and the library holds no communicator; the only per-(device, stream) state it keeps is the GEMM's tile-queue counter
- * table described at tnr_gemm_queue_reset. */
+/* Every entry point is a single-device operation on the stream passed last, except the collectives tnr_comm_* at the end of
+ * this file (the gradient exchange of the data-parallel step: RCCL behind a communicator the caller creates and owns); the
+ * only per-(device, stream) state the library keeps is the GEMMs' tile-queue counter table described at tnr_gemm_queue_reset. */
 
 /* ---- encoder --------------------------------------------------------------------------------- */
 
@@ -110,13 +109,14 @@ int64_t tnr_gemm_colsum_rows(int64_t M);
 /* Debug / test hooks.  tnr_gemm_nt_route: which kernel tnr_gemm_nt(_ex) launches for a shape on the current
  * device (the decision depends on (M, N, K, flags) and the CU count only) -- the parity tests assert it so that
  * every tile variant is pinned at the shapes the training step issues.  tnr_gemm_set_option: process-wide A/B
- * switches for tools/ ("ver", "gm", "fine_pct", "allow_fine", "bm", "nt", "pp", "tnpp", "mix"; "cus" = n: plan and size the
+ * switches for tools/ ("ver", "gm", "fine_pct", "allow_fine", "bm", "mix"; "pp" / "tnpp" = 0: never the queue-fed persistent
+ * kernels of the NT GEMM / the weight gradient, which then take the 256x128 or 128x128 kernels; "cus" = n: plan and size the
  * persistent GEMM grids for n compute units instead of the device's, 0 = the device's - same results, pinned by
  * test_gemm_grids_sized_for_fewer_cus_bit_exact); the library never reads the environment and the defaults are the shipped
  * configuration. */
 #define TNR_ROUTE_128x128 128    /* 128x128 tile, 4 waves, 2 workgroups per CU */
-#define TNR_ROUTE_256x128 2128   /* 256x128 tile (N % 256 != 0) */
-#define TNR_ROUTE_256x256 256    /* 256x256 tile, 8 waves */
+#define TNR_ROUTE_256x128 2128   /* 256x128 tile, 8 waves (N % 256 != 0, or option "pp" = 0) */
+#define TNR_ROUTE_256x256 256    /* 256x256 tile, 8 waves, persistent (tile queue) */
 #define TNR_ROUTE_224x256 224    /* 224-row variant of the same kernel (fewer wasted rows per round) */
 int tnr_gemm_nt_route(int64_t M, int64_t N, int64_t K, int flags);
 int tnr_gemm_set_option(const char* key, int value);
@@ -125,13 +125,14 @@ int tnr_gemm_set_option(const char* key, int value);
  * at row (32 * mi - 32) * p + 32 * floor(p * tall / panels).  Chosen so that panels * N / 256 tiles fill whole rounds of the
  * workgroups (option "mix" = 0: one height).  Results do not depend on the tiling (a row's K order is the same). */
 int tnr_gemm_nt_plan(int64_t M, int64_t N, int flags, int n_cu, int* mi, int* panels, int* tall);
-/* The persistent 256-column GEMM kernel (tnr_gemm_nt* on the TNR_ROUTE_256x256 / 224x256 routes) hands out its tiles through
- * nine 32-bit counters per (device, stream) pair, kept in a 128-entry table inside the library (a __device__ array; 288 KB).
- * A pair is bound at its first launch (its counters are zeroed by a hipMemsetAsync on that stream) and every completed launch
- * returns them to zero, so launches need no workspace argument.  The table is never drained and the current device is never
- * changed: the 129th distinct pair is refused with TNR_EUNSUPPORTED (run fewer streams, or tnr_gemm_set_option("pp", 0) for
- * the non-persistent kernel).  tnr_gemm_queue_reset zeroes the calling stream's counters again (stream-ordered): only needed
- * after a launch on that stream was aborted (a device fault survived by the process), never in normal operation.
+/* The persistent GEMM kernels (tnr_gemm_nt* on the TNR_ROUTE_256x256 / 224x256 routes, and the weight gradient's for N and K
+ * multiples of 256) hand out their tiles through nine 32-bit counters per (device, stream) pair, kept in a 128-entry table
+ * inside the library (a __device__ array; 288 KB).  A pair is bound at its first launch (its counters are zeroed by a
+ * hipMemsetAsync on that stream) and every completed launch returns them to zero, so launches need no workspace argument.
+ * The table is never drained and the current device is never changed: the 129th distinct pair is refused with
+ * TNR_EUNSUPPORTED (run fewer streams, or tnr_gemm_set_option("pp", 0) and ("tnpp", 0) for the kernels without a tile
+ * queue).  tnr_gemm_queue_reset zeroes the calling stream's counters again (stream-ordered): only needed after a launch on
+ * that stream was aborted (a device fault survived by the process), never in normal operation.
  * (Test hooks such as the CU hog live in libtnr_testhooks.so, built beside this library for tests/ and tools/ only.) */
 int tnr_gemm_queue_reset(void* stream);
 /* Measurement hook (bench.py's `box` object; no reference counterpart - the reference never reports a clock): while `buf` is

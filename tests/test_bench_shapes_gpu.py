@@ -65,7 +65,7 @@ def _expected_route(M, N, flags, n_cu=256):
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 @pytest.mark.parametrize("name,N,K,flags", NT_LAUNCHES)
-def test_gemm_nt_main_loop_bit_exact_at_bench_shape(dtype, name, N, K, flags):
+def test_gemm_nt_main_loop_bit_exact_at_bench_shape(dtype, name, N, K, flags, route=None):
     M = M_BENCH
     rs = np.random.RandomState(N + K)
     A = rs.randint(-3, 4, (M, K)).astype(np.float32)
@@ -74,9 +74,11 @@ def test_gemm_nt_main_loop_bit_exact_at_bench_shape(dtype, name, N, K, flags):
     A[:, 1] += np.arange(M) % 3
     a, b = torch.from_numpy(A).to(DEV), torch.from_numpy(Bm).to(DEV)
     c = torch.full((M + 64, N), 7.0, device=DEV, dtype=torch.float32)
-    route = T.query("tnr_gemm_nt_route" + _sfx(dtype), M, N, K, F32O)
-    if PIN_ROUTES[0] and torch.cuda.get_device_properties(0).multi_processor_count == 256:
-        assert route == _expected_route(M, N, F32O), (name, route)
+    got = T.query("tnr_gemm_nt_route" + _sfx(dtype), M, N, K, F32O)
+    if route is not None:                            # a caller's explicit expectation (option "pp" = 0: no CU dependence)
+        assert got == route, (name, got)
+    elif PIN_ROUTES[0] and torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        assert got == _expected_route(M, N, F32O), (name, got)
     T.call("tnr_gemm_nt" + _sfx(dtype), a.to(TD[dtype]), K, b.to(TD[dtype]), K, c, N, M, N, K, None, None, 0, None, 0, F32O)
     full = a @ b.T                                    # fp32 GPU product: exact for these integers (|sum| < 2^24)
     torch.cuda.synchronize()
@@ -90,7 +92,7 @@ def test_gemm_nt_main_loop_bit_exact_at_bench_shape(dtype, name, N, K, flags):
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 @pytest.mark.parametrize("name,N,K,flags", NT_LAUNCHES)
-def test_gemm_nt_epilogues_at_bench_shape(dtype, name, N, K, flags):
+def test_gemm_nt_epilogues_at_bench_shape(dtype, name, N, K, flags, route=None):
     M, td = M_BENCH, TD[dtype]
     g = torch.Generator(device=DEV).manual_seed(N * 7 + K + flags)
     rnd = lambda *s, sc=1.0: (torch.randn(*s, device=DEV, generator=g) * sc)
@@ -100,9 +102,13 @@ def test_gemm_nt_epilogues_at_bench_shape(dtype, name, N, K, flags):
     aux = rnd(M, N).to(td) if flags & MD else (torch.zeros((M, N), device=DEV, dtype=td) if flags & AUX else None)
     aux_in = aux.clone() if flags & MD else None
     c = torch.zeros((M, N), device=DEV, dtype=torch.float32 if flags & F32O else td)
-    cs = torch.zeros((T.query("tnr_gemm_colsum_rows" + _sfx(dtype), M), N), device=DEV) if flags & CS else None
-    if PIN_ROUTES[0] and torch.cuda.get_device_properties(0).multi_processor_count == 256:
-        assert T.query("tnr_gemm_nt_route" + _sfx(dtype), M, N, K, flags) == _expected_route(M, N, flags), name
+    # partial rows prefilled: every row of tnr_gemm_colsum_rows(M) is the kernel's, whatever the buffer held
+    cs = torch.full((T.query("tnr_gemm_colsum_rows" + _sfx(dtype), M), N), 7.0, device=DEV) if flags & CS else None
+    got = T.query("tnr_gemm_nt_route" + _sfx(dtype), M, N, K, flags)
+    if route is not None:
+        assert got == route, (name, got)
+    elif PIN_ROUTES[0] and torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        assert got == _expected_route(M, N, flags), name
     T.call("tnr_gemm_nt_ex" + _sfx(dtype), a, K, b, K, c, N, M, N, K, bias, res, N if res is not None else 0, aux,
            N if aux is not None else 0, flags, cs)
     torch.cuda.synchronize()
@@ -131,16 +137,24 @@ def test_gemm_nt_epilogues_at_bench_shape(dtype, name, N, K, flags):
         np.testing.assert_allclose(cs.sum(0).cpu().numpy(), want_cs, rtol=1e-4, atol=1e-2, err_msg=name + "/colsum")
 
 
-def test_gemm_nt_plain_loop_variant_bit_exact():
-    """The 256-row routes have two main loops in the library (tnr_gemm_set_option "pp": 1 = the persistent ping-pong kernel, the
-    default; 0 = the plain two-buffer loop with the LDS-staged epilogue): the other one stays pinned on every launch shape too."""
+# tnr_gemm_set_option "pp" = 0: the route of every NT launch with the epilogue flags (the main-loop check's fp32 output always takes
+# the 256x128 kernel); the GELU / GELU' epilogues stay on the 128x128 kernel's table GELU
+NT_ROUTES_WITHOUT_QUEUE = {"qkv": T.ROUTE_256x128, "attn_out": T.ROUTE_256x128, "ffn_up_kept": T.ROUTE_128,
+                           "ffn_up_frozen": T.ROUTE_128, "ffn_down": T.ROUTE_256x128, "pool_fc1": T.ROUTE_256x128,
+                           "dgrad_pool": T.ROUTE_256x128, "dgrad_w2_geluprime": T.ROUTE_128, "dgrad_w1": T.ROUTE_256x128,
+                           "dgrad_o": T.ROUTE_256x128, "dgrad_qkv": T.ROUTE_256x128}
+
+
+def test_gemm_nt_without_tile_queue_bit_exact():
+    """tnr_gemm_set_option "pp" = 0 never launches the queue-fed persistent kernel (the way out when the (device, stream) table is
+    full): every launch shape of the step then takes the 256x128 or 128x128 kernel, pinned, bit-exact and against numpy too."""
     L = T.lib()
     try:
         assert L.tnr_gemm_set_option(b"pp", 0) == 0
         for name, N, K, flags in NT_LAUNCHES:
-            test_gemm_nt_main_loop_bit_exact_at_bench_shape("fp16", name, N, K, flags)
-            test_gemm_nt_epilogues_at_bench_shape("fp16", name, N, K, flags)
-        test_gemm_nt_epilogues_at_bench_shape("bf16", *NT_LAUNCHES[2])
+            test_gemm_nt_main_loop_bit_exact_at_bench_shape("fp16", name, N, K, flags, route=T.ROUTE_256x128)
+            test_gemm_nt_epilogues_at_bench_shape("fp16", name, N, K, flags, route=NT_ROUTES_WITHOUT_QUEUE[name])
+        test_gemm_nt_epilogues_at_bench_shape("bf16", *NT_LAUNCHES[2], route=NT_ROUTES_WITHOUT_QUEUE[NT_LAUNCHES[2][0]])
     finally:
         L.tnr_gemm_set_option(b"pp", PP_DEFAULT)
 
@@ -205,8 +219,8 @@ def test_gemm_tn_wgrad_bit_exact_at_bench_shape(dtype, name, N, K):
 
 
 def test_gemm_tn_wgrad_plain_loop_variant_bit_exact():
-    """The weight-gradient kernel's other main loop (tnr_gemm_set_option "tnpp" = 0: plain two-buffer loop; the default is the
-    ping-pong schedule) on the same launches."""
+    """The weight gradient without the queue-fed persistent kernel (tnr_gemm_set_option "tnpp" = 0: the 256x128 kernel; the default
+    is the persistent register-staged ping-pong loop) on the same launches."""
     L = T.lib()
     try:
         assert L.tnr_gemm_set_option(b"tnpp", 0) == 0
@@ -218,11 +232,10 @@ def test_gemm_tn_wgrad_plain_loop_variant_bit_exact():
 
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
 def test_gemm_tn_wgrad_register_staged_variant_bit_identical(dtype):
-    """The weight-gradient kernel's two main loops (tnr_gemm_set_option "tnpp": 0 = the plain two-buffer loop, operands by LDS-DMA +
-    transposing fragment reads; 2 = the persistent ping-pong loop, operands through registers, transposed there, fragment-ready LDS
-    image - the default) feed every MFMA the same operand registers in the same order: integer-exact on the step's launches, and
-    the SAME BITS on random operands.  (Rounds 3-5 kept a third loop, tnpp = 1 - LDS-DMA under the ping-pong schedule - as the
-    middle term of this comparison; round 6 removed it from the library.)"""
+    """The weight gradient's two main loops (tnr_gemm_set_option "tnpp": 0 = the 256x128 kernel, operands by LDS-DMA + transposing
+    fragment reads; 2 = the persistent ping-pong loop, operands through registers, transposed there, fragment-ready LDS image - the
+    default) feed every MFMA the same operand registers in the same order: integer-exact on the step's launches, and the SAME BITS
+    on random operands.  (tnpp = 0 ran a plain 256x256 loop before; it gave these bits too.)"""
     L = T.lib()
     M, Mp = M_BENCH, (M_BENCH + 127) // 128 * 128
     try:

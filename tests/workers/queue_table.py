@@ -79,7 +79,7 @@ except T.TnrError:
     refused_f16 = True
 rc_reset2 = L.tnr_gemm_queue_reset(streams[0].cuda_stream)
 after_reset2 = others_ok(streams[0]) and gemm_ok(streams[0])
-L.tnr_gemm_set_option(b"pp", 0)                                      # the documented way out: the non-persistent kernel needs no slot
+L.tnr_gemm_set_option(b"pp", 0)                                      # the documented way out: the 256x128 kernel needs no slot
 plain_on_refused = gemm_ok(streams[-1])
 L.tnr_gemm_set_option(b"pp", 1)
 print(json.dumps(dict(ok=ok, refused_at=refused_at, msg=msg, again=again, rc_reset=rc_reset, after_reset=after_reset,

@@ -18,7 +18,7 @@ void tnr_set_error(const char* fmt, ...) {
 extern "C" const char* tnr_last_error(void) { return g_err; }
 extern "C" int tnr_version(void) { return 1; }
 
-static TnrGemmOpts g_gemm_opts = {3, 8, 60, 1, 0, 0, 1, 2, 1, 0, nullptr, 0};
+static TnrGemmOpts g_gemm_opts = {3, 8, 60, 1, 0, 1, 2, 1, 0, nullptr, 0};
 TnrGemmOpts* tnr_gemm_opts() { return &g_gemm_opts; }
 
 extern "C" int tnr_gemm_set_option(const char* key, int value) {
@@ -29,7 +29,6 @@ extern "C" int tnr_gemm_set_option(const char* key, int value) {
     else if (!strcmp(key, "fine_pct")) o.fine_pct = value;
     else if (!strcmp(key, "allow_fine")) o.allow_fine = value;
     else if (!strcmp(key, "bm")) o.bm = value;
-    else if (!strcmp(key, "nt")) o.nt = value;
     else if (!strcmp(key, "pp")) o.pp = value;
     else if (!strcmp(key, "tnpp")) o.tnpp = value;
     else if (!strcmp(key, "mix")) o.mix = value;

@@ -40,9 +40,10 @@ struct TnrGemmOpts {
     int fine_pct;    // 256x256 grid fill (percent of the CUs) below which the 128x128 kernel is used
     int allow_fine;  // 0 = never fall back to the 128x128 kernel for sparse grids
     int bm;          // 0 = pick the tile height per launch ; 224 / 256 = force it
-    int nt;          // 1 = non-temporal accesses for once-touched epilogue operands
-    int pp;          // 1 = ping-pong main loop (two wave groups staggered by a barrier), 0 = plain two-buffer loop
-    int tnpp;        // weight gradient: non-zero (default 2) = register-staged persistent ping-pong loop, 0 = plain two-buffer loop
+    int pp;          // NT: non-zero (default 1) = the persistent ping-pong kernel on the 256x256 routes, 0 = never the queue-fed
+                     // kernel (those launches take the 256x128 / 128x128 kernels, which need no tile-queue slot)
+    int tnpp;        // weight gradient: non-zero (default 2) = the persistent register-staged kernel, 0 = never the queue-fed kernel
+                     // (the 256x128 kernel instead)
     int mix;         // ping-pong NT kernel: 1 = row panels of two heights so that the tiles fill whole rounds, 0 = one height
     int cus;         // 0 = plan and size the persistent GEMM grids for the device's CUs ; n = for n of them (two kernels side by side)
     void* clock_buf; // tnr_gemm_clock_stamps: device buffer of clock_n (cycles, 100 MHz ticks) pairs the persistent NT kernel fills, or NULL

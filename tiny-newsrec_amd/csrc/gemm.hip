@@ -28,13 +28,14 @@ struct NTArgs {
     int flags;
     float* colsum_part;        // TNR_EPI_COLSUM: (rows_of_partials, N) fp32, one row per 64-row strip of C
     int gm;                    // rasterisation group height
-    int nt;                    // 1: streaming (non-temporal) accesses for once-touched epilogue operands
+    int nt;                    // unused, the host writes 0: the slot of a removed option, kept like `probe` below - dropping a slot
+                               // changed the persistent kernels' scalar-load schedule (EXPERIMENTS.md item 44)
     int tile0;                 // first logical tile of this launch (0: one launch per GEMM)
     TnrDrop drop;              // TNR_EPI_DROPOUT: the site whose mask multiplies (acc + bias [-> activation]) before the residual add
     int mix_p, mix_x;          // ping-pong kernel: mix_p row panels, mix_x of them full height (32 MI rows), the others 32 rows
                                // shorter, spread evenly (pp_panel); mix_x == mix_p: the uniform tiling
     unsigned* queue;           // ping-pong kernel: 8 tile counters (one per XCD label) + a done counter, all zero between launches
-    int probe;                 // unused by the product: the slot the probe builds' switches take (tools/probes/README.md); kept so that the
+    int probe;                 // unused by the product: the slot the probe builds' switches take (tools/probes/build.sh); kept so that the
                                // kernel arguments of both builds have ONE layout (the kernels' scalar loads are scheduled around it)
     unsigned long long* clock; // ping-pong kernel, measurement hook (tnr_gemm_clock_stamps): workgroup b < clock_n writes the shader
     int clock_n;               // cycles (s_memtime) and 100 MHz ticks (s_memrealtime) of its life at clock[2 b], clock[2 b + 1]; NULL = off
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(NTArgs g) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    // the same table GELU as the 256x256 kernel: results must not depend on which kernel a launch is routed to
+    // the same table GELU as the persistent kernel: results must not depend on which kernel a launch is routed to
     f32x2* lut = (f32x2*)(smem + 2 * BUF_BYTES);
     const bool use_lut = (g.flags & (TNR_EPI_GELU | TNR_EPI_MULDGELU)) != 0;
     if (use_lut) lut_build(lut, (g.flags & TNR_EPI_MULDGELU) != 0);
@@ -622,242 +623,16 @@ __global__ __launch_bounds__(512, 2) void gemm_tn256_kernel(TNArgs g) {
     }
 }
 
-// ---- row-contiguous epilogue of the 256x256 kernels -------------------------------------------------
-// The accumulator layout gives a lane 4 consecutive n of one row: 8-byte bf16 accesses, 16 rows per wave
-// instruction.  Measured: an extra bf16 tensor written/read that way (AUXOUT / RES / MULDGELU) cost +220..290 us
-// per 52800x3072 launch while an fp32 output (16-byte accesses, twice the bytes) cost +40 us -- the epilogue is
-// bound by the number of small memory transactions.  So the fp32 tile goes through LDS in two passes of 128 rows
-// ([128][256] fp32, rows padded by 16 B) and is post-processed with thread -> (row, 8 consecutive columns):
-// 16-byte residual / aux loads and C / aux stores, two full 512-byte row segments per wave instruction.
-constexpr int EPI_LD = 256 * 4 + 16;                 // bytes per staged row
-constexpr int EPI_BYTES = 128 * EPI_LD;              // 133,120 B
-constexpr int LDS3_BYTES = EPI_BYTES + LUT_N * 8;
-
-// Optional streaming (non-temporal) accesses for the epilogue's once-touched operands (C / side-output stores, residual /
-// pre-activation loads), env TNR_GEMM_NT=1.  Measured with an interleaved same-box A/B over seven shapes: within +-0.8 %
-// of plain accesses (an earlier "+7 %" was box-to-box variance), so the default is plain.
-#ifndef TNR_GEMM_NT
-#define TNR_GEMM_NT 1
-#endif
-#if TNR_GEMM_NT
-#define TNR_NT_STORE(v, p) do { if (g.nt) __builtin_nontemporal_store((v), (p)); else *(p) = (v); } while (0)
-#define TNR_NT_LOAD(p) (g.nt ? __builtin_nontemporal_load((p)) : *(p))
-#else
-#define TNR_NT_STORE(v, p) (*(p) = (v))
-#define TNR_NT_LOAD(p) (*(p))
-#endif
-
-// MI x NJ 16x16 accumulator blocks per wave, NTHR threads per workgroup (8 waves of 128x64 or 4 waves of 128x128)
-template <int MI, int NJ = 4, int NTHR = 512>
-__device__ __forceinline__ void nt_epilogue_coalesced(const NTArgs& g, f32x4 (&acc)[MI][NJ], char* smem, const f32x2* lut,
-                                                      int bm, int bn, int wm, int wn, int lane) {
-    constexpr int PR = 16 * MI;          // rows per pass (= rows per wave), tile height 2 * PR
-    constexpr int RG = NTHR / 32;        // row groups working on a pass
-    constexpr int ITER = PR / RG;        // rows per thread and pass
-    const int flags = g.flags;
-    const int tid = threadIdx.x;
-    const int c8 = (tid & 31) * 8, rg = tid >> 5;            // 8 columns, row group 0..15
-    const int n = bn * 256 + c8;
-    f32x4 b0 = (f32x4){0.f, 0.f, 0.f, 0.f}, b1 = b0;
-    if (flags & TNR_EPI_BIAS) {
-        b0 = *(const f32x4*)(g.bias + n);
-        b1 = *(const f32x4*)(g.bias + n + 4);
-    }
-    float cs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) cs[e] = 0.f;
-    // The residual / pre-activation rows are HBM reads the arithmetic below waits for (an extra 16-bit M x N operand
-    // cost +50 us per 52800x3072 launch with the loads issued where they are used): pass 0's are issued before the
-    // accumulators are staged, pass 1's while pass 0 is being processed.
-    // One prefetched operand per launch (the engine never combines RES with MULDGELU; if both are set the residual
-    // is read where it is used).
-    const bool pre_aux = (flags & TNR_EPI_MULDGELU) != 0;
-    const bool pre_res = !pre_aux && (flags & TNR_EPI_RES) != 0;
-    bf16x8 xx[2][ITER];
-    auto issue_loads = [&](int pass) {
-        const int m0 = bm * (2 * PR) + pass * PR;
-        if (pre_aux | pre_res) {
-            const bf16* src = pre_aux ? g.aux : g.res;
-            const int64_t ld = pre_aux ? g.ldaux : g.ldres;
-#pragma unroll
-            for (int it = 0; it < ITER; ++it) {
-                int m = m0 + rg + RG * it;
-                m = m < g.M ? m : g.M - 1;
-                xx[pass][it] = TNR_NT_LOAD((const bf16x8*)(src + (int64_t)m * ld + n));
-            }
-        }
-    };
-    issue_loads(0);
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        __syncthreads();                                       // staging area free (K loop / previous pass done)
-        if (wm == pass) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    *(f32x4*)(smem + (i * 16 + (lane & 15)) * EPI_LD + (wn * (NJ * 16) + j * 16 + (lane >> 4) * 4) * 4) = acc[i][j];
-        }
-        __syncthreads();
-        const int m0 = bm * (2 * PR) + pass * PR;
-        if (pass == 0) issue_loads(1);
-#pragma unroll
-        for (int it = 0; it < ITER; ++it) {
-            const int row = rg + RG * it;
-            const int m = m0 + row;
-            if (m >= g.M) continue;
-            f32x4 v0 = *(const f32x4*)(smem + row * EPI_LD + c8 * 4) + b0;
-            f32x4 v1 = *(const f32x4*)(smem + row * EPI_LD + c8 * 4 + 16) + b1;
-            float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            if (flags & TNR_EPI_AUXOUT) {
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16)v[e];
-                TNR_NT_STORE(o, (bf16x8*)(g.aux + (int64_t)m * g.ldaux + n));
-            }
-            if (flags & TNR_EPI_GELU) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = lut_eval<false>(lut, v[e]);
-            }
-            if (flags & TNR_EPI_TANH) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = tnr_tanh(v[e]);
-            }
-            if (flags & TNR_EPI_MULDGELU) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] *= lut_eval<true>(lut, (float)xx[pass][it][e]);
-            }
-            if (flags & TNR_EPI_DROPOUT) {
-                float dm[8];
-                tnr_drop8(g.drop, ((uint64_t)m * g.N + n) >> 3, dm);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] *= dm[e];
-            }
-            if (flags & TNR_EPI_RES) {
-                bf16x8 r = pre_res ? xx[pass][it] : *(const bf16x8*)(g.res + (int64_t)m * g.ldres + n);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] += (float)r[e];
-            }
-            if (flags & TNR_EPI_OUTF32) {
-                float* c = (float*)g.C + (int64_t)m * g.ldc + n;
-                TNR_NT_STORE(((f32x4){v[0], v[1], v[2], v[3]}), (f32x4*)c);
-                TNR_NT_STORE(((f32x4){v[4], v[5], v[6], v[7]}), (f32x4*)(c + 4));
-            } else {
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    o[e] = (bf16)v[e];
-                    cs[e] += (float)o[e];
-                }
-                TNR_NT_STORE(o, (bf16x8*)((bf16*)g.C + (int64_t)m * g.ldc + n));
-            }
-        }
-    }
-    if (flags & TNR_EPI_COLSUM) {
-        // column sums of the 256-row tile: 16 row groups hold partials for the same 8 columns
-        __syncthreads();
-        float* red = (float*)smem;                             // [RG][256]
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[rg * 256 + c8 + e] = cs[e];
-        __syncthreads();
-        if (tid < 256) {
-            float t = 0.f;
-#pragma unroll
-            for (int r = 0; r < RG; ++r) t += red[r * 256 + tid];
-            float* pr = g.colsum_part + (int64_t)(bm * 4) * g.N + bn * 256 + tid;   // 4 partial rows per row-tile (v2 layout)
-            pr[0] = t;
-            pr[g.N] = 0.f;
-            pr[2 * (int64_t)g.N] = 0.f;
-            pr[3 * (int64_t)g.N] = 0.f;
-        }
-    }
-}
-
 // ================================================================================================
-// v3: 256x256 output tile, 8 waves (2 x 4, each 128 x 64), two 64 KB LDS stages
-// ([A rows 0-127 | A rows 128-255 | B rows 0-127 | B rows 128-255], 16 KB each).  128 FLOP per staged byte:
-// measured on MI355X the v2 load pipeline alone (no MFMA) took 80% of the kernel time, i.e. these GEMMs are
-// bound by the ~10-12 TB/s the CUs can stream from L2 into LDS, so the tile has to grow, not the schedule.
+// LDS of the persistent 256x256 kernels: two 64 KB K stages ([A rows 0-127 | A rows 128-255 | B rows 0-127 | B rows 128-255],
+// 16 KB each; the register-staged weight-gradient kernel keeps its dY / X images there), behind them the NT kernel's two 1 KiB
+// bias buffers and its GELU table, then the tile-queue answer (PP_LDS, RS_LDS).  128 FLOP per staged byte: measured on MI355X
+// the 256x128 load pipeline alone (no MFMA) took 80% of its kernel time, i.e. these GEMMs are bound by the ~10-12 TB/s the CUs
+// can stream from L2 into LDS, so the tile has to grow, not the schedule.  The sizes set the kernels' occupancy.
 constexpr int STAGE3 = 4 * TILE_BYTES;
 constexpr int RING3 = 2 * STAGE3;
-
-// MI = 16-row MFMA tiles per wave along M: tile height BM = 32 * MI (256 or 224).  The host picks the height
-// that minimises ceil(tiles / CUs) * BM for the launch (e.g. N = 768: 621 tiles of 256 rows = 3 rounds on 256 CUs;
-// 708 tiles of 224 rows are 3 rounds too, each 12.5 % shorter).
-template <int MI>
-__global__ __launch_bounds__(512, 2) void gemm_nt256x256_kernel(NTArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int PR = 16 * MI, BM = 2 * PR;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w >> 2, wn = w & 3;
-    const int nbn = g.N >> 8;
-    const int nbm = (g.M + BM - 1) / BM;
-    const int wg = g.tile0 + xcd_remap(blockIdx.x, gridDim.x);      // gridDim.x = tiles of this launch
-    int bm, bn;
-    tile_coords(wg, nbm, nbn, g.gm, bm, bn);
-
-    const bf16* src[8];
-    int dst[8];
-    bool live[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        int p = w * 8 + q, sub = p >> 4, pp = p & 15;
-        int row = pp * 8 + (lane >> 3);
-        int chunk = (lane & 7) ^ (row & 7);
-        live[q] = sub >= 2 || pp * 8 < PR;                 // A sub-tiles hold PR rows (PR/8 pieces of 8 rows)
-        if (sub < 2) {
-            int gm = bm * BM + sub * PR + row;
-            gm = gm < g.M ? gm : g.M - 1;
-            src[q] = g.A + (int64_t)gm * g.lda + chunk * 8;
-        } else {
-            src[q] = g.B + (int64_t)(bn * 256 + (sub - 2) * 128 + row) * g.ldb + chunk * 8;
-        }
-        dst[q] = sub * TILE_BYTES + pp * 1024;
-    }
-    auto stage = [&](int buf, int kt) {
-        char* base = smem + buf * STAGE3;
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            if (MI == 8 || live[q]) glds16(src[q] + kt * 64, base + dst[q]);     // wave-uniform predicate
-    };
-    int foff[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) foff[s] = (lane & 15) * 128 + ((((4 * s) + (lane >> 4)) ^ (lane & 7)) << 4);
-
-    f32x4 acc[MI][4];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    f32x2* lut = (f32x2*)(smem + EPI_BYTES);             // own LDS region, built while the first loads fly
-    if (g.flags & (TNR_EPI_GELU | TNR_EPI_MULDGELU)) lut_build(lut, (g.flags & TNR_EPI_MULDGELU) != 0);
-    const int nk = g.K >> 6;
-    stage(0, 0);
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cur = kt & 1;
-        TNR_WAIT_VMCNT(0);
-        __builtin_amdgcn_s_barrier();            // tile kt landed everywhere; tile kt-1 fully consumed
-        if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
-        const char* sa = smem + cur * STAGE3 + wm * TILE_BYTES;
-        const char* sb = smem + cur * STAGE3 + (2 + (wn >> 1)) * TILE_BYTES + ((wn & 1) * 64) * 128;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            bf16x8 af[MI], bfr[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bfr[j] = *(const bf16x8*)(sb + j * 16 * 128 + foff[s]);
-#pragma unroll
-            for (int i = 0; i < MI; ++i) af[i] = *(const bf16x8*)(sa + i * 16 * 128 + foff[s]);
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = TNR_MFMA_16x16x32(bfr[j], af[i], acc[i][j], 0, 0, 0);
-        }
-    }
-    nt_epilogue_coalesced<MI>(g, acc, smem, lut, bm, bn, wm, wn, lane);
-}
-
+constexpr int PP_LUT = RING3 + 2 * 1024;             // 133,120 B
+constexpr int LDS3_BYTES = PP_LUT + LUT_N * 8;
 // ---- epilogue of the ping-pong kernel: no transposes, no LDS staging ----------------------------------
 // The MFMA is called with the B fragment first, so lane (m = lane & 15, q = lane >> 4) holds, in register r of block j,
 // the output of row m and of the B row that lane 4 q + r fed into block j.  WHICH B row that is is free: the kernel's
@@ -1068,7 +843,7 @@ __device__ __forceinline__ void nt_epilogue_cols(const NTArgs& g, f32x4 (&acc)[M
 }
 
 // ================================================================================================
-// v8 "ping-pong": the v3 tile (256 x 256 x 64, 8 waves of 128 x 64, two 64 KB K stages) with the two wave groups of a
+// v8 "ping-pong": a 256 x 256 x 64 tile (8 waves of 128 x 64, two 64 KB K stages) with the two wave groups of a
 // SIMD staggered by one barrier.  Waves w and w + 4 share a SIMD; group 0 (w < 4, rows 0-127) and group 1 (rows 128-255)
 // alternate between a LOAD segment (fragment ds_reads + the LDS-DMA of a later half tile) and an MFMA segment (16 MFMAs:
 // one 64 x 32 quadrant of the wave's 128 x 64 over K = 64), so that while one wave of a SIMD issues MFMAs its partner's
@@ -1224,7 +999,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(NTArgs g) {
         for (int s = 0; s < 2; ++s) boff[s] = rb * 128 + ((((4 * s) + (lane >> 4)) ^ pp_bswz(rb)) << 4);
     }
 
-    f32x2* lut = (f32x2*)(smem + EPI_BYTES);             // own LDS region, built while the queue answers
+    f32x2* lut = (f32x2*)(smem + PP_LUT);                // own LDS region, built while the queue answers
     if (flags & (TNR_EPI_GELU | TNR_EPI_MULDGELU)) lut_build(lut, (flags & TNR_EPI_MULDGELU) != 0);
     pp_q_wait(q0);
     if (tid == 0) qlds[0] = c0 + (int)q0;
@@ -1380,105 +1155,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(NTArgs g) {
     tile = next;
   }
   leave();
-}
-
-// wgrad v3: output tile 256 (n) x 256 (k); stage = [dY cols 0-127 | dY cols 128-255 | X cols 0-127 | X cols 128-255]
-__global__ __launch_bounds__(512, 2) void gemm_tn256x256_kernel(TNArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wn = w >> 2, wk = w & 3;          // wave tile: 128 n x 64 k
-    const int nbk = g.K >> 8;
-    const int ntile = (g.N >> 8) * nbk;
-    const int wg = xcd_remap(blockIdx.x, ntile * g.splits);
-    const int z = wg / ntile, tile = wg - z * ntile;
-    const int bn = tile / nbk, bk = tile - bn * nbk;
-    const int mt0 = z * g.tiles_per_split;
-    int mt1 = mt0 + g.tiles_per_split;
-    if (mt1 > g.Mt) mt1 = g.Mt;
-    const int nt = mt1 - mt0;
-
-    const bf16* src[8];
-    int64_t ldsrc[8];
-    int dst[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        int p = w * 8 + q, sub = p >> 4, pp = p & 15;
-        int row = pp * 4 + (lane >> 4);
-        int chunk = (lane & 15) ^ tn_swz(row);
-        if (sub < 2) {
-            src[q] = g.dY + (int64_t)(mt0 * 64 + row) * g.lddy + bn * 256 + sub * 128 + chunk * 8;
-            ldsrc[q] = 64 * g.lddy;
-        } else {
-            src[q] = g.X + (int64_t)(mt0 * 64 + row) * g.ldx + bk * 256 + (sub - 2) * 128 + chunk * 8;
-            ldsrc[q] = 64 * g.ldx;
-        }
-        dst[q] = sub * TILE_BYTES + pp * 1024;
-    }
-    auto stage = [&](int buf, int t) {
-        char* base = smem + buf * STAGE3;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) glds16(src[q] + (int64_t)t * ldsrc[q], base + dst[q]);
-    };
-    const int g16 = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
-    int roff[2][2], rswz[2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int row = 32 * s + 8 * g16 + q4 + 4 * h;
-            roff[s][h] = row * 256 + (p4 & 1) * 8;
-            rswz[s][h] = tn_swz(row);
-        }
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    if (nt > 0) {
-        stage(0, 0);
-        for (int t = 0; t < nt; ++t) {
-            const int cur = t & 1;
-            TNR_WAIT_VMCNT(0);
-            __builtin_amdgcn_s_barrier();
-            if (t + 1 < nt) stage(cur ^ 1, t + 1);
-            const char* sy = smem + cur * STAGE3 + wn * TILE_BYTES;
-            const char* sx = smem + cur * STAGE3 + (2 + (wk >> 1)) * TILE_BYTES;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                bf16x8 yf[8], xf[4];
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    int cx = 2 * ((wk & 1) * 4 + tt) + (p4 >> 1);
-                    bf16x4 x0 = ds_read_tr16(sx + roff[s][0] + ((cx ^ rswz[s][0]) << 4));
-                    bf16x4 x1 = ds_read_tr16(sx + roff[s][1] + ((cx ^ rswz[s][1]) << 4));
-                    xf[tt] = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-#pragma unroll
-                for (int tt = 0; tt < 8; ++tt) {
-                    int cy = 2 * tt + (p4 >> 1);
-                    bf16x4 y0 = ds_read_tr16(sy + roff[s][0] + ((cy ^ rswz[s][0]) << 4));
-                    bf16x4 y1 = ds_read_tr16(sy + roff[s][1] + ((cy ^ rswz[s][1]) << 4));
-                    yf[tt] = __builtin_shufflevector(y0, y1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[i][j] = TNR_MFMA_16x16x32(xf[j], yf[i], acc[i][j], 0, 0, 0);
-            }
-        }
-    }
-    float* slab = g.ws + (int64_t)z * g.N * g.K;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int n = bn * 256 + wn * 128 + i * 16 + (lane & 15);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int k = bk * 256 + wk * 64 + j * 16 + (lane >> 4) * 4;
-            *(f32x4*)(slab + (int64_t)n * g.K + k) = acc[i][j];
-        }
-    }
 }
 
 
@@ -1792,7 +1468,7 @@ struct PpPlan { int mi, P, x; };
 static PpPlan pp_plan(int64_t M, int64_t N, int flags, int n_cu) {
     const TnrGemmOpts& o = *tnr_gemm_opts();
     const int64_t ncol = N / 256;
-    if ((flags & TNR_EPI_COLSUM) || !o.mix || !o.pp) {
+    if ((flags & TNR_EPI_COLSUM) || !o.mix) {
         const int64_t t256 = ((M + 255) / 256) * ncol, t224 = ((M + 223) / 224) * ncol;
         const int64_t c256 = ((t256 + n_cu - 1) / n_cu) * 256, c224 = ((t224 + n_cu - 1) / n_cu) * 224;
         bool use224 = c224 * 108 < c256 * 100 && !(flags & TNR_EPI_COLSUM);   // per-tile fixed costs: need a clear win
@@ -1822,12 +1498,14 @@ static PpPlan pp_plan(int64_t M, int64_t N, int flags, int n_cu) {
 
 static int nt_route(int64_t M, int64_t N, int64_t K, int flags, int n_cu) {
     const TnrGemmOpts& o = *tnr_gemm_opts();
+    // 256x256 tiles: the persistent kernel, for N % 256 == 0 unless option "pp" = 0 rules out its tile queue
+    const bool t256 = (N % 256) == 0 && o.pp;
     // short inputs (stage-1 title / body passes, small eval batches): when the 256x256 grid would leave more than 40 % of
     // the CUs without a tile, the 128x128 kernel (2 workgroups per CU) spreads the same work four times finer
-    const bool sparse256 = (N % 256) == 0 && ((M + 255) / 256) * (N / 256) * 100 < (int64_t)n_cu * o.fine_pct && !(flags & TNR_EPI_COLSUM);
-    const bool odd_gelu = (N % 256) != 0 && (flags & (TNR_EPI_GELU | TNR_EPI_MULDGELU));   // the 256x128 kernel has no table GELU
+    const bool sparse256 = t256 && ((M + 255) / 256) * (N / 256) * 100 < (int64_t)n_cu * o.fine_pct && !(flags & TNR_EPI_COLSUM);
+    const bool odd_gelu = !t256 && (flags & (TNR_EPI_GELU | TNR_EPI_MULDGELU));   // the 256x128 kernel has no table GELU
     if (o.ver == 1 || M <= 128 || odd_gelu || (sparse256 && o.allow_fine)) return TNR_ROUTE_128x128;
-    if (o.ver == 2 || (N % 256) != 0) return TNR_ROUTE_256x128;
+    if (o.ver == 2 || !t256) return TNR_ROUTE_256x128;
     return pp_plan(M, N, flags, n_cu).mi == 7 ? TNR_ROUTE_224x256 : TNR_ROUTE_256x256;
 }
 
@@ -1874,7 +1552,7 @@ unsigned* tnr_pp_queue_of(void* stream, bool reset) {
     if (!set) {
         if (nslot == PP_QUEUE_SETS) {
             tnr_set_error("tnr_gemm_nt: more than %d (device, stream) pairs have launched the persistent GEMM in this process "
-                          "(reuse streams, or tnr_gemm_set_option(\"pp\", 0) for the kernel without a tile queue)", PP_QUEUE_SETS);
+                          "(reuse streams, or tnr_gemm_set_option(\"pp\", 0) for the kernels without a tile queue)", PP_QUEUE_SETS);
             return nullptr;
         }
         slots[nslot] = Slot{dev, st};
@@ -1951,7 +1629,7 @@ extern "C" int TNR_NAME(tnr_gemm_nt_do)(const void* A, int64_t lda, const void* 
                   "tnr_gemm_nt: TNR_EPI_COLSUM needs a partial buffer, bf16 output and M > 128");
     const TnrGemmOpts& o = *tnr_gemm_opts();
     NTArgs g{(const bf16*)A, lda, (const bf16*)B, ldb, C, ldc, (int)M, (int)N, (int)K, bias,
-             (const bf16*)res, ldres, (bf16*)aux, ldaux, flags, colsum_part, o.gm > 0 ? o.gm : 8, o.nt, 0, dd, 0, 0, nullptr, 0, nullptr, 0};
+             (const bf16*)res, ldres, (bf16*)aux, ldaux, flags, colsum_part, o.gm > 0 ? o.gm : 8, 0, 0, dd, 0, 0, nullptr, 0, nullptr, 0};
     g.clock = (unsigned long long*)o.clock_buf;
     g.clock_n = o.clock_n;
 #define TNR_PP_ATTR(CF)                                                                                                     \
@@ -1960,8 +1638,6 @@ extern "C" int TNR_NAME(tnr_gemm_nt_do)(const void* A, int64_t lda, const void* 
     TNR_ONCE_PER_DEVICE({
         (void)hipFuncSetAttribute((const void*)gemm_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF_BYTES + LUT_N * 8);
         (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RING2);
-        (void)hipFuncSetAttribute((const void*)gemm_nt256x256_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS3_BYTES);
-        (void)hipFuncSetAttribute((const void*)gemm_nt256x256_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS3_BYTES);
         TNR_PP_FLAG_SETS(TNR_PP_ATTR)
         TNR_PP_ATTR(-1)
     });
@@ -1970,29 +1646,26 @@ extern "C" int TNR_NAME(tnr_gemm_nt_do)(const void* A, int64_t lda, const void* 
     const int n_cu = device_cus();
     switch (nt_route(M, N, K, flags, n_cu)) {
     case TNR_ROUTE_128x128:
+        // column sums: two partial rows per 128-row tile; after an odd number of tiles the last two of tnr_gemm_colsum_rows(M) get zeros
+        if ((flags & TNR_EPI_COLSUM) && ((M + 127) / 128) % 2 &&
+            hipMemsetAsync(colsum_part + ((M + 127) / 128) * 2 * N, 0, 2 * N * sizeof(float), st) != hipSuccess) {
+            tnr_set_error("tnr_gemm_nt: could not zero the last column-sum rows");
+            return TNR_ELAUNCH;
+        }
         hipLaunchKernelGGL(gemm_nt_kernel, dim3((unsigned)(((M + 127) / 128) * (N / 128))), dim3(256), 2 * BUF_BYTES + LUT_N * 8, st, g);
         break;
     case TNR_ROUTE_256x128:
         hipLaunchKernelGGL(gemm_nt256_kernel, dim3((unsigned)(((M + 255) / 256) * (N / 128))), dim3(512), RING2, st, g);
         break;
-    case TNR_ROUTE_224x256:
-        if (o.pp) {
-            const PpPlan pl = pp_plan(M, N, flags, n_cu);
-            g.mix_p = pl.P; g.mix_x = pl.x;
-            if (!(g.queue = pp_queue_of(st))) return TNR_EUNSUPPORTED;
-            pp_launch<7>(g, (unsigned)std::min<int64_t>((int64_t)pl.P * (N / 256), std::max(n_cu, 8)), st);   // >= 8: every XCD label needs a workgroup
-        }
-        else hipLaunchKernelGGL((gemm_nt256x256_kernel<7>), dim3((unsigned)(((M + 223) / 224) * (N / 256))), dim3(512), LDS3_BYTES, st, g);
+    default: {                                          // the persistent kernel, 224- or 256-row instance
+        const PpPlan pl = pp_plan(M, N, flags, n_cu);
+        g.mix_p = pl.P; g.mix_x = pl.x;
+        if (!(g.queue = pp_queue_of(st))) return TNR_EUNSUPPORTED;
+        const unsigned grid = (unsigned)std::min<int64_t>((int64_t)pl.P * (N / 256), std::max(n_cu, 8));   // >= 8: every XCD label needs a workgroup
+        if (pl.mi == 7) pp_launch<7>(g, grid, st);
+        else pp_launch<8>(g, grid, st);
         break;
-    default:
-        if (o.pp) {
-            const PpPlan pl = pp_plan(M, N, flags, n_cu);
-            g.mix_p = pl.P; g.mix_x = pl.x;
-            if (!(g.queue = pp_queue_of(st))) return TNR_EUNSUPPORTED;
-            pp_launch<8>(g, (unsigned)std::min<int64_t>((int64_t)pl.P * (N / 256), std::max(n_cu, 8)), st);
-        }
-        else hipLaunchKernelGGL((gemm_nt256x256_kernel<8>), dim3((unsigned)(((M + 255) / 256) * (N / 256))), dim3(512), LDS3_BYTES, st, g);
-        break;
+    }
     }
     TNR_CHECK_LAUNCH("tnr_gemm_nt");
     return TNR_OK;
@@ -2021,7 +1694,7 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_ex)(const void* dY, int64_t lddy, cons
     int tps = (Mt + splits - 1) / splits;
     splits = (Mt + tps - 1) / tps;
     TNArgs g{(const bf16*)dY, lddy, (const bf16*)X, ldx, ws, Mt, (int)N, (int)K, tps, splits, nullptr};
-    const int ver = tnr_gemm_opts()->ver;
+    const TnrGemmOpts& o = *tnr_gemm_opts();
     // gemm_tn_rs_kernel addresses a unit's rows through a raw buffer with 32-bit byte offsets (its pipeline also issues the loads
     // of two m steps past the unit's end and relies on them falling OUTSIDE the buffer): a unit must stay under 2 GiB per operand
     TNR_CHECK_ARG(tn_rs_unit_fits(tps, lddy, ldx),
@@ -2029,29 +1702,24 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_ex)(const void* dY, int64_t lddy, cons
                   tps * 64, (long)std::max(lddy, ldx));
     TNR_ONCE_PER_DEVICE({
         (void)hipFuncSetAttribute((const void*)gemm_tn256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RING2);
-        (void)hipFuncSetAttribute((const void*)gemm_tn256x256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RING3);
         (void)hipFuncSetAttribute((const void*)gemm_tn_rs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS);
     });
-    if (ver == 1 || (N % 256) != 0) {
+    if (o.ver == 1 || (N % 256) != 0) {
         dim3 grid((unsigned)((N / 128) * (K / 128) * splits));
         hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(256), 2 * BUF_BYTES, (hipStream_t)stream, g);
-    } else if (ver == 2 || (K % 256) != 0) {
+    } else if (o.ver == 2 || (K % 256) != 0 || !o.tnpp) {     // tnpp = 0: no tile queue
         dim3 grid((unsigned)((N / 256) * (K / 128) * splits));
         hipLaunchKernelGGL(gemm_tn256_kernel, grid, dim3(512), RING2, (hipStream_t)stream, g);
     } else {
-        dim3 grid((unsigned)((N / 256) * (K / 256) * splits));
-        if (tnr_gemm_opts()->tnpp) {
-            // persistent: at most one workgroup per CU (and at least one per XCD label) pulls the (split, tile) units
-            TNGroup grp{};
-            grp.p[0] = g;
-            for (int i = 1; i <= TN_MAXP; ++i) grp.ubase[i] = (int)grid.x;
-            tn_group_ranges(grp, 1);
-            if (!(grp.queue = pp_queue_of((hipStream_t)stream))) return TNR_EUNSUPPORTED;
-            const int n_cu = device_cus();
-            dim3 pgrid((unsigned)std::min<int64_t>((int64_t)grid.x, std::max(n_cu, 8)));
-            hipLaunchKernelGGL(gemm_tn_rs_kernel, pgrid, dim3(512), RS_LDS, (hipStream_t)stream, grp);
-        }
-        else hipLaunchKernelGGL(gemm_tn256x256_kernel, grid, dim3(512), RING3, (hipStream_t)stream, g);
+        // persistent: at most one workgroup per CU (and at least one per XCD label) pulls the (split, tile) units
+        const int units = (int)((N / 256) * (K / 256) * splits);
+        TNGroup grp{};
+        grp.p[0] = g;
+        for (int i = 1; i <= TN_MAXP; ++i) grp.ubase[i] = units;
+        tn_group_ranges(grp, 1);
+        if (!(grp.queue = pp_queue_of((hipStream_t)stream))) return TNR_EUNSUPPORTED;
+        dim3 pgrid((unsigned)std::min<int64_t>(units, std::max(device_cus(), 8)));
+        hipLaunchKernelGGL(gemm_tn_rs_kernel, pgrid, dim3(512), RS_LDS, (hipStream_t)stream, grp);
     }
     TNR_CHECK_LAUNCH("tnr_gemm_tn_wgrad");
     int64_t NK = N * K;
@@ -2072,9 +1740,7 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_group)(const tnr_wgrad_problem_t* p, i
                               p[i].out_scale == p[i - 1].out_scale,
                           "tnr_gemm_tn_wgrad_group: problem %d continues problem %d but differs from it in dW / N / K / lddw / out_scale", i, i - 1);
     auto head_of = [&](int i) { while (p[i].accumulate == 2) --i; return i; };
-    bool pp = tnr_gemm_opts()->tnpp && tnr_gemm_opts()->ver == 3 && n > 1;
-    for (int i = 0; i < n; ++i) pp = pp && p[i].N >= 256 && p[i].K >= 256 && (p[i].N % 256) == 0 && (p[i].K % 256) == 0;
-    if (!pp) {                                 // a shape off the persistent kernel's route (or one problem): one launch each, the same results
+    auto one_by_one = [&]() {                  // one launch per problem, the same results
         for (int i = 0; i < n; ++i) {
             // (a chained problem - accumulate 2 - simply adds to what its predecessor wrote; the head's workspace serves both in turn)
             int rc = TNR_NAME(tnr_gemm_tn_wgrad_ex)(p[i].dY, p[i].lddy, p[i].X, p[i].ldx, p[i].dW, p[i].lddw, p[i].M, p[i].N, p[i].K,
@@ -2083,7 +1749,10 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_group)(const tnr_wgrad_problem_t* p, i
             if (rc != TNR_OK) return rc;
         }
         return TNR_OK;
-    }
+    };
+    bool pp = tnr_gemm_opts()->tnpp && tnr_gemm_opts()->ver == 3 && n > 1;
+    for (int i = 0; i < n; ++i) pp = pp && p[i].N >= 256 && p[i].K >= 256 && (p[i].N % 256) == 0 && (p[i].K % 256) == 0;
+    if (!pp) return one_by_one();              // a shape off the persistent kernel's route (or one problem)
     TNGroup grp{};
     SlabGroup sg{};
     int64_t units = 0, maxblk = 0;
@@ -2119,15 +1788,8 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_group)(const tnr_wgrad_problem_t* p, i
     }
     if (units < 8) {
         // fewer units than XCD labels: the grid min(units, ...) would leave labels that tn_group_ranges gives work without a
-        // workgroup (their units never computed, the slab sum reading unwritten slabs) -> one launch per problem, the same results
-        for (int i = 0; i < n; ++i) {
-            // (a chained problem - accumulate 2 - simply adds to what its predecessor wrote; the head's workspace serves both in turn)
-            int rc = TNR_NAME(tnr_gemm_tn_wgrad_ex)(p[i].dY, p[i].lddy, p[i].X, p[i].ldx, p[i].dW, p[i].lddw, p[i].M, p[i].N, p[i].K,
-                                                     p[i].accumulate == 2 ? p[head_of(i)].ws : p[i].ws, p[i].splits,
-                                                     p[i].accumulate == 2 ? 1 : p[i].accumulate, p[i].out_scale, stream);
-            if (rc != TNR_OK) return rc;
-        }
-        return TNR_OK;
+        // workgroup (their units never computed, the slab sum reading unwritten slabs) -> one launch per problem
+        return one_by_one();
     }
     for (int i = n; i <= TN_MAXP; ++i) grp.ubase[i] = (int)units;
     tn_group_ranges(grp, n);

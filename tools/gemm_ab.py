@@ -1,6 +1,6 @@
 """Interleaved same-process A/B of a library GEMM option (tnr_gemm_set_option) over the encoder's NT shapes; GPU box.
 Box-to-box variance on this pool is up to 15 %, so only interleaved same-box comparisons are meaningful.
-    AB=pp:0:1 python tools/gemm_ab.py        (two-phase main loop vs ping-pong)      DTYPE=fp16|bf16   M=rows   OPT=key=val,... (fixed for both sides)
+    AB=pp:0:1 python tools/gemm_ab.py        (256x128 / 128x128 kernels vs ping-pong) DTYPE=fp16|bf16   M=rows   OPT=key=val,... (fixed for both sides)
     PROBE=8 ... : the same A/B in the probe build (tools/_probe, -DTNR_PROBES=2) with that probe set, e.g. 8 = K loops without epilogues"""
 import collections, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

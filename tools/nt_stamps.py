@@ -2,7 +2,8 @@
 on the forward / dgrad GEMM; GPU box, probe build:
     tools/probes/build.sh _ntst -DTNR_NT_STAMPS
     N=3072 K=768 FLAGS=1 python tools/nt_stamps.py
-Intervals of a K tile (group 0's numbering; group 1 runs one barrier behind): L0 M0 L1 M1 L2 M2 L3 M3, 16 MFMAs per M."""
+Intervals of a K tile (group 0's numbering; group 1 runs one barrier behind): L0 M0 L1 M1 L2 M2 L3 M3, 16 MFMAs per M.
+PP=0 (option "pp" = 0) routes the launch to the 256x128 / 128x128 kernels, which take no stamps: the launch time alone."""
 import ctypes, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
