@@ -383,6 +383,18 @@ int tnr_gemm_nt_do(const void* A, int64_t lda, const void* B, int64_t ldb, void*
 int tnr_ln_bwd_do(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
                   float* dgamma, float* dbeta, float* dxsum, float* part, int64_t M, int H, void* dxm,
                   const tnr_dropout_t* drop, void* stream);
+/* The same two with a row-major site split at a row (stage 1's joint passes: the body pass's token rows laid directly behind
+ * the title pass's, one launch over both): rows [0, split_row) under `drop`, rows [split_row, M) under `drop_tail` (same seed,
+ * site and p, its own call) with the row index counted from split_row - exactly the masks of the two per-pass _do calls.
+ * drop_tail NULL or split_row == M: bit-identical to the _do call.  TNR_EINVAL if the sites differ in seed, site or p, or if
+ * split_row is outside [0, M]. */
+int tnr_gemm_nt_do_split(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                         int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
+                         void* aux, int64_t ldaux, int flags, float* colsum_part, const tnr_dropout_t* drop,
+                         const tnr_dropout_t* drop_tail, int64_t split_row, void* stream);
+int tnr_ln_bwd_do_split(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
+                        float* dgamma, float* dbeta, float* dxsum, float* part, int64_t M, int H, void* dxm,
+                        const tnr_dropout_t* drop, const tnr_dropout_t* drop_tail, int64_t split_row, void* stream);
 /* attention with dropout on the normalised probabilities (:224); backward regenerates the mask */
 int tnr_attn_l32_fwd_do(const void* qkv, const float* mask_add, const float* rel, void* ctx, int64_t n_seq, int L, int A,
                         const tnr_dropout_t* drop, void* stream);
@@ -397,6 +409,9 @@ int tnr_attn_long_bwd_do(const void* qkv, const float* mask_add, const float* re
  * probabilities (pairs = n_seq * A, L, L) through the per-query (by_columns = 0) or per-key (1) device accessor */
 int tnr_dropout_mask(const tnr_dropout_t* drop, int64_t rows, int64_t cols, float* out, void* stream);
 int tnr_dropout_mask_probs(const tnr_dropout_t* drop, int64_t pairs, int L, int by_columns, float* out, void* stream);
+/* tnr_dropout_mask of a site split at a row (the rule of the *_do_split entry points) */
+int tnr_dropout_mask_split(const tnr_dropout_t* drop, const tnr_dropout_t* drop_tail, int64_t split_row, int64_t rows, int64_t cols,
+                           float* out, void* stream);
 
 /* ---- optimiser ------------------------------------------------------------------------------- */
 
@@ -509,6 +524,13 @@ int tnr_gemm_nt_do_f16(const void* A, int64_t lda, const void* B, int64_t ldb, v
 int tnr_ln_bwd_do_f16(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
                   float* dgamma, float* dbeta, float* dxsum, float* part, int64_t M, int H, void* dxm,
                   const tnr_dropout_t* drop, void* stream);
+int tnr_gemm_nt_do_split_f16(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                             int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
+                             void* aux, int64_t ldaux, int flags, float* colsum_part, const tnr_dropout_t* drop,
+                             const tnr_dropout_t* drop_tail, int64_t split_row, void* stream);
+int tnr_ln_bwd_do_split_f16(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
+                            float* dgamma, float* dbeta, float* dxsum, float* part, int64_t M, int H, void* dxm,
+                            const tnr_dropout_t* drop, const tnr_dropout_t* drop_tail, int64_t split_row, void* stream);
 int tnr_attn_l32_fwd_do_f16(const void* qkv, const float* mask_add, const float* rel, void* ctx, int64_t n_seq, int L, int A,
                         const tnr_dropout_t* drop, void* stream);
 int tnr_attn_l32_bwd_do_f16(const void* qkv, const float* mask_add, const float* rel, const void* dctx, void* dqkv,

@@ -79,7 +79,7 @@ unsigned* tnr_pp_queue_of(void* stream, bool reset);
 // public dropout descriptor (host memory, may be NULL = off) -> kernel argument
 #include "dropout.h"
 static inline int tnr_make_drop(const tnr_dropout_t* d, TnrDrop* o, const char* who) {
-    *o = TnrDrop{0u, 0u, 0u, 0u, 0u, 1.0f};
+    *o = TnrDrop{0u, 0u, 0u, 0u, 0u, 1.0f, 0u, 0xFFFFFFFFu};
     if (!d || d->p <= 0.0) return TNR_OK;
     if (!(d->p < 1.0)) { tnr_set_error("%s: dropout p must be in [0, 1)", who); return TNR_EINVAL; }
     o->k0 = (uint32_t)d->seed;
@@ -90,6 +90,21 @@ static inline int tnr_make_drop(const tnr_dropout_t* d, TnrDrop* o, const char* 
     // p below 2^-17 rounds to "keep everything": then nothing is scaled either (forward kernels test thresh, backward ones
     // multiply by scale -- both must see the same effective dropout)
     o->scale = o->thresh ? (float)(1.0 / (1.0 - d->p)) : 1.0f;
+    return TNR_OK;
+}
+// a row-major site split at row `split` of M: rows [0, split) under `d`, rows [split, M) under `tail` (same seed / site / p,
+// its own call; rows counted from split) - the masks of the two passes' own launches.  tail NULL or split == M: `d` alone.
+static inline int tnr_make_drop_split(const tnr_dropout_t* d, const tnr_dropout_t* tail, int64_t split, int64_t M, TnrDrop* o,
+                                      const char* who) {
+    if (int rc = tnr_make_drop(d, o, who)) return rc;
+    if (split < 0 || split > M || M > (int64_t)0xFFFFFFFF) { tnr_set_error("%s: split row %ld outside [0, %ld]", who, (long)split, (long)M); return TNR_EINVAL; }
+    if (!tail || split == M) return TNR_OK;
+    if (!d || d->seed != tail->seed || d->site != tail->site || d->p != tail->p) {
+        tnr_set_error("%s: the two halves of a split site must share seed, site and p", who);
+        return TNR_EINVAL;
+    }
+    o->call_tail = tail->call;
+    o->split = (uint32_t)split;
     return TNR_OK;
 }
 

@@ -5,6 +5,9 @@
 // gives eight 16-bit uniforms; an element is kept iff its uniform >= thresh = floor(p * 65536 + 0.5) and kept elements are
 // scaled by 1 / (1 - p).  Nothing is stored: the backward kernels regenerate the same bits from the same counter.
 //   row-major (rows, cols) sites:  element e = row * cols + col -> call e >> 3, uniform e & 7
+//                                  split at a row (two passes laid one behind the other, stage 1's joint passes): rows
+//                                  m < split are (call, m), rows m >= split (call_tail, m - split) - the masks of the two
+//                                  passes' own launches (tnr_drop_row)
 //   attention probabilities:       4 x 4 (query, key) blocks -> call ((pair * nb + q >> 2) * nb + k >> 2) * 2 + ((q & 3) >> 1),
 //                                  uniform ((q & 1) << 2) | (k & 3) ; pair = n * A + a, nb = Lr / 4
 // oracle/dropout_oracle.py restates this bit for bit (tnr_dropout_mask dumps the multipliers for the tests).
@@ -16,6 +19,8 @@ struct TnrDrop {
     uint32_t site, call;   // counter words 2, 3
     uint32_t thresh;       // 0 = dropout off
     float scale;           // 1 / (1 - p)
+    uint32_t call_tail;    // counter word 3 of the rows at and behind `split` (row-major sites only)
+    uint32_t split;        // first row of the tail; 0xFFFFFFFF = no tail
 };
 
 #define TNR_DROP_EMB 0
@@ -40,25 +45,33 @@ __device__ __forceinline__ void tnr_philox(uint32_t c0, uint32_t c1, uint32_t c2
     o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
 }
 
-// the eight multipliers (0 or scale) of Philox call `ci`
-__device__ __forceinline__ void tnr_drop8(const TnrDrop& d, uint64_t ci, float (&m)[8]) {
+// a row of a row-major site -> (forward-call word, row index within its pass): the split rule, in one place
+__device__ __forceinline__ uint32_t tnr_drop_row(const TnrDrop& d, uint32_t m, uint32_t& call) {
+    const bool tail = m >= d.split;
+    call = tail ? d.call_tail : d.call;
+    return tail ? m - d.split : m;
+}
+
+// the eight multipliers (0 or scale) of Philox call `ci` under forward-call word `call`
+__device__ __forceinline__ void tnr_drop8(const TnrDrop& d, uint32_t call, uint64_t ci, float (&m)[8]) {
     uint32_t o[4];
-    tnr_philox((uint32_t)ci, (uint32_t)(ci >> 32), d.site, d.call, d.k0, d.k1, o);
+    tnr_philox((uint32_t)ci, (uint32_t)(ci >> 32), d.site, call, d.k0, d.k1, o);
 #pragma unroll
     for (int e = 0; e < 8; ++e) m[e] = ((o[e >> 1] >> (16 * (e & 1))) & 0xFFFFu) >= d.thresh ? d.scale : 0.f;
 }
 
 // four consecutive elements e0 .. e0 + 3 of a row-major site (e0 % 4 == 0)
-__device__ __forceinline__ void tnr_drop4(const TnrDrop& d, uint64_t e0, float (&m)[4]) {
+__device__ __forceinline__ void tnr_drop4(const TnrDrop& d, uint32_t call, uint64_t e0, float (&m)[4]) {
     uint32_t o[4];
     const uint64_t ci = e0 >> 3;
-    tnr_philox((uint32_t)ci, (uint32_t)(ci >> 32), d.site, d.call, d.k0, d.k1, o);
+    tnr_philox((uint32_t)ci, (uint32_t)(ci >> 32), d.site, call, d.k0, d.k1, o);
     const uint32_t w0 = (e0 & 4) ? o[2] : o[0], w1 = (e0 & 4) ? o[3] : o[1];
     m[0] = (w0 & 0xFFFFu) >= d.thresh ? d.scale : 0.f;
     m[1] = (w0 >> 16) >= d.thresh ? d.scale : 0.f;
     m[2] = (w1 & 0xFFFFu) >= d.thresh ? d.scale : 0.f;
     m[3] = (w1 >> 16) >= d.thresh ? d.scale : 0.f;
 }
+__device__ __forceinline__ void tnr_drop4(const TnrDrop& d, uint64_t e0, float (&m)[4]) { tnr_drop4(d, d.call, e0, m); }
 
 // attention probabilities, one query x four consecutive keys (k0 % 4 == 0): multipliers of (q, k0 .. k0 + 3)
 __device__ __forceinline__ void tnr_drop_prob_row(const TnrDrop& d, uint64_t pair, int nb, int q, int k0, float (&m)[4]) {

@@ -173,8 +173,13 @@ __device__ __forceinline__ void nt_epilogue(const NTArgs& g, f32x4 (&acc)[4][4],
                 }
             }
             if (flags & TNR_EPI_DROPOUT) {      // BertSelfOutput / BertOutput: dense -> dropout -> + residual
+                // the mask product is rounded on its own (never contracted into the residual add): every NT kernel then gives a
+                // row the same bits, whichever route its launch takes (stage 1's joint launch vs the two per-pass ones)
+#pragma clang fp contract(off)
                 float dm[4];
-                tnr_drop4(g.drop, (uint64_t)m * g.N + n, dm);
+                uint32_t dc;
+                const uint32_t mr = tnr_drop_row(g.drop, (uint32_t)m, dc);       // rows behind a split: the tail pass's own mask
+                tnr_drop4(g.drop, dc, (uint64_t)mr * g.N + n, dm);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] *= dm[r];
             }
@@ -769,11 +774,14 @@ __device__ __forceinline__ void nt_epilogue_cols(const NTArgs& g, f32x4 (&acc)[M
             }
         }
         if (flags & TNR_EPI_DROPOUT) {
+#pragma clang fp contract(off)     // as in nt_epilogue: the mask product rounded on its own, the same bits on every route
             float dm[8];
-            tnr_drop8(g.drop, ((uint64_t)m * g.N + n0) >> 3, dm);
+            uint32_t dc;
+            const uint32_t mr = tnr_drop_row(g.drop, (uint32_t)m, dc);
+            tnr_drop8(g.drop, dc, ((uint64_t)mr * g.N + n0) >> 3, dm);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] *= dm[e];
-            tnr_drop8(g.drop, ((uint64_t)m * g.N + n0 + 32) >> 3, dm);
+            tnr_drop8(g.drop, dc, ((uint64_t)mr * g.N + n0 + 32) >> 3, dm);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[8 + e] *= dm[e];
         }
@@ -1432,6 +1440,10 @@ extern "C" int TNR_NAME(tnr_gemm_nt_do)(const void* A, int64_t lda, const void* 
                               int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
                               void* aux, int64_t ldaux, int flags, float* colsum_part, const tnr_dropout_t* drop,
                               void* stream);
+extern "C" int TNR_NAME(tnr_gemm_nt_do_split)(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                                    int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
+                                    void* aux, int64_t ldaux, int flags, float* colsum_part, const tnr_dropout_t* drop,
+                                    const tnr_dropout_t* drop_tail, int64_t split_row, void* stream);
 
 extern "C" int TNR_NAME(tnr_gemm_nt)(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                            int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
@@ -1609,8 +1621,16 @@ extern "C" int TNR_NAME(tnr_gemm_nt_do)(const void* A, int64_t lda, const void* 
                               int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
                               void* aux, int64_t ldaux, int flags, float* colsum_part, const tnr_dropout_t* drop,
                               void* stream) {
+    return TNR_NAME(tnr_gemm_nt_do_split)(A, lda, B, ldb, C, ldc, M, N, K, bias, res, ldres, aux, ldaux, flags, colsum_part, drop,
+                                          nullptr, M, stream);
+}
+
+extern "C" int TNR_NAME(tnr_gemm_nt_do_split)(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                                    int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
+                                    void* aux, int64_t ldaux, int flags, float* colsum_part, const tnr_dropout_t* drop,
+                                    const tnr_dropout_t* drop_tail, int64_t split_row, void* stream) {
     TnrDrop dd;
-    if (int rc = tnr_make_drop(drop, &dd, "tnr_gemm_nt")) return rc;
+    if (int rc = tnr_make_drop_split(drop, drop_tail, split_row, M, &dd, "tnr_gemm_nt")) return rc;
     TNR_CHECK_ARG(!(flags & TNR_EPI_DROPOUT), "tnr_gemm_nt: TNR_EPI_DROPOUT is set by passing a dropout site");
     if (dd.thresh) flags |= TNR_EPI_DROPOUT;
     TNR_CHECK_ARG(A && B && C, "tnr_gemm_nt: null operand");

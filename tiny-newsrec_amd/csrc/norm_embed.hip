@@ -186,7 +186,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* __restrict__ dy
                 // gradient is dx * mask / (1 - p) (second output, what its wgrad / dgrad / bias gradient consume), the
                 // residual branch takes dx itself
                 float dm[8];
-                tnr_drop8(drop, ((uint64_t)m * H + v * 256 + hl * 8) >> 3, dm);
+                uint32_t dc;
+                const uint32_t mr = tnr_drop_row(drop, (uint32_t)m, dc);     // rows behind a split: the tail pass's own mask
+                tnr_drop8(drop, dc, ((uint64_t)mr * H + v * 256 + hl * 8) >> 3, dm);
                 bf16x8 om;
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
@@ -540,11 +542,14 @@ extern "C" int tnr_reduce_rows(const float* part, int64_t rows, int64_t stride, 
 
 #ifndef TNR_BUILD_F16
 // the multipliers of a dropout site as fp32 (tests: statistics, bit equality with oracle/dropout_oracle.py)
-__global__ void dropout_mask_rows_kernel(float* __restrict__ out, int64_t n4, TnrDrop d) {
+__global__ void dropout_mask_rows_kernel(float* __restrict__ out, int64_t n4, int64_t cols, TnrDrop d) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
     float m[4];
-    tnr_drop4(d, (uint64_t)i * 4, m);
+    const int64_t row = i * 4 / cols;
+    uint32_t dc;
+    const uint32_t mr = tnr_drop_row(d, (uint32_t)row, dc);
+    tnr_drop4(d, dc, (uint64_t)mr * cols + (i * 4 - row * cols), m);
     *(f32x4*)(out + i * 4) = (f32x4){m[0], m[1], m[2], m[3]};
 }
 // attention probabilities (pairs, L, L): thread = (pair, query, key group of 4) through the row accessor, or (cols != 0) the
@@ -569,11 +574,16 @@ __global__ void dropout_mask_probs_kernel(float* __restrict__ out, int64_t pairs
     }
 }
 extern "C" int tnr_dropout_mask(const tnr_dropout_t* drop, int64_t rows, int64_t cols, float* out, void* stream) {
+    return tnr_dropout_mask_split(drop, nullptr, rows, rows, cols, out, stream);
+}
+extern "C" int tnr_dropout_mask_split(const tnr_dropout_t* drop, const tnr_dropout_t* drop_tail, int64_t split_row, int64_t rows,
+                                      int64_t cols, float* out, void* stream) {
     TnrDrop dd;
-    if (int rc = tnr_make_drop(drop, &dd, "tnr_dropout_mask")) return rc;
+    if (int rc = tnr_make_drop_split(drop, drop_tail, split_row, rows, &dd, "tnr_dropout_mask")) return rc;
     TNR_CHECK_ARG(out && rows >= 1 && cols >= 4 && (cols % 4) == 0, "tnr_dropout_mask: need cols %% 4 == 0");
     int64_t n4 = rows * cols / 4;
-    hipLaunchKernelGGL(dropout_mask_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n4, dd);
+    hipLaunchKernelGGL(dropout_mask_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n4, cols,
+                       dd);
     TNR_CHECK_LAUNCH("tnr_dropout_mask");
     return TNR_OK;
 }
@@ -609,9 +619,14 @@ extern "C" int tnr_reduce_multi(const int64_t* desc, int n_blocks, void* stream)
 extern "C" int TNR_NAME(tnr_ln_bwd_do)(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
                              float* dgamma, float* dbeta, float* dxsum, float* part, int64_t M, int H, void* dxm,
                              const tnr_dropout_t* drop, void* stream) {
+    return TNR_NAME(tnr_ln_bwd_do_split)(dy, x, stats, gamma, dx, dgamma, dbeta, dxsum, part, M, H, dxm, drop, nullptr, M, stream);
+}
+extern "C" int TNR_NAME(tnr_ln_bwd_do_split)(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
+                                   float* dgamma, float* dbeta, float* dxsum, float* part, int64_t M, int H, void* dxm,
+                                   const tnr_dropout_t* drop, const tnr_dropout_t* drop_tail, int64_t split_row, void* stream) {
     // dgamma == dbeta == dxsum == NULL with part != NULL: partials only, the caller reduces them (tnr_reduce_multi)
     TnrDrop dd;
-    if (int rc = tnr_make_drop(drop, &dd, "tnr_ln_bwd")) return rc;
+    if (int rc = tnr_make_drop_split(drop, drop_tail, split_row, M, &dd, "tnr_ln_bwd")) return rc;
     TNR_CHECK_ARG(dxm || !dd.thresh, "tnr_ln_bwd: an active dropout site needs the masked second output");
     TNR_CHECK_ARG(dy && x && stats && gamma && dx && M >= 1, "tnr_ln_bwd: null pointer");
     TNR_CHECK_ARG(H == 768 || H == 256 || H == 512 || H == 1024, "tnr_ln_bwd: H must be 256/512/768/1024");

@@ -433,6 +433,13 @@ class Engine:
             z = lambda *s_: torch.zeros(s_, device=self.dev, dtype=self.tdt)
             self.dyprem, self.dh1prem = z(self.Mp, self.cfg.H), z(self.Mp, self.cfg.H)
 
+    def _begin_drop_call(self, train=True):
+        """Number the forward call that starts now (encode(); Stage1Engine's joint passes call it once per pass)."""
+        self.drop_cur = None
+        if self.drop is not None and train:
+            self.drop_cur = dict(self.drop, call=2 * self.drop_calls + self.drop["pass_id"])
+            self.drop_calls += 1
+
     def _dsite(self, kind, layer):
         """tnr_dropout_t of one site of the CURRENT forward call (None when dropout is off for that kind)."""
         d = self.drop_cur
@@ -616,12 +623,15 @@ class Engine:
         return splits, T.query("tnr_gemm_tn_ws_elems", N, K, splits)
 
     # ------------------------------------------------------------------ kernel wrappers
-    def _gemm(self, a, w, c, M, bias=None, res=None, aux=None, flags=0, colsum=None, drop=None):
+    def _gemm(self, a, w, c, M, bias=None, res=None, aux=None, flags=0, colsum=None, drop=None, drop_tail=None, split_row=None):
+        """drop_tail / split_row: rows [split_row, M) under the site drop_tail (tnr_gemm_nt_do_split; stage 1's joint passes)."""
         N, K = w.shape
         args = (a, a.stride(0), w, w.stride(0), c, c.stride(0), M, N, K, bias, res,
                 res.stride(0) if res is not None else 0, aux, aux.stride(0) if aux is not None else 0, flags, colsum)
         if drop is None:
             self._c("tnr_gemm_nt_ex", *args)
+        elif drop_tail is not None:
+            self._c("tnr_gemm_nt_do_split", *args, drop, drop_tail, split_row)
         else:
             self._c("tnr_gemm_nt_do", *args, drop)
 
@@ -804,10 +814,7 @@ class Engine:
         g = self.p
         if self._rel_stale:
             self.refresh_rel()
-        self.drop_cur = None
-        if self.drop is not None and train:
-            self.drop_cur = dict(self.drop, call=2 * self.drop_calls + self.drop["pass_id"])
-            self.drop_calls += 1
+        self._begin_drop_call(train)
         ds = self._dsite
         fc = getattr(self, "fcache", None) if self.drop_cur is None else None      # a cached prefix has no fresh masks
         first = 0

@@ -221,6 +221,8 @@ def train(args):
             idx = torch.from_numpy(idx_h).to(dev)
             body_idx = torch.from_numpy(np.ascontiguousarray(idx_h[:, 0])).to(dev) if idx_h.dtype == np.int32 else None
             losses, score = eng.forward_indexed(d_title, d_body, idx, label, d_tt, d_tb, body_idx=body_idx)
+            if ep == 0 and cnt == 1:          # which form the step takes (Stage1Engine._joint_ok): once, beside the dropout line
+                logging.info("[%d] stage %d: %s", rank, args.stage, "joint passes" if eng.ran_joint else "per-pass")
             sums[0] += eng.total_loss()
             sums[1] += losses[1]
             sums[2] += losses[0]

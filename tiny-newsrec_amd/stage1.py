@@ -13,13 +13,16 @@ One model, two sequence lengths: two Engine instances share parameters / gradien
 weight copies and own their workspaces.  Their backwards run in step, layer by layer: the bias / LayerNorm sums of the title pass
 are written and those of the body pass added; every weight gradient is ONE chained problem over the title rows and the body rows
 (tnr_gemm_tn_wgrad_group, accumulate = 2).
-Round 6 - JOINT passes (`Stage1Engine.joint`, the default without dropout): a Linear, a LayerNorm and a weight gradient act on token
+Round 6 - JOINT passes (`Stage1Engine.joint`, the default, with dropout or without): a Linear, a LayerNorm and a weight gradient act on token
 rows one by one, so the body pass's rows are laid directly BEHIND the title pass's in every per-token buffer and each of them is
 ONE launch over M = N Lt + B Lb rows instead of one per pass (8 896 rows at 30 / 128, 24 064 at 24 / 512: tile orders large enough
 for the persistent 256-wide kernels); only what depends on the sequence length - embeddings, attention, pooling - still runs per
 pass, on its row range (one stream: `joint_streams` puts the body's on a second one, measured slower).  A layer's four weight
 gradients leave in ONE grouped persistent launch whose units share one round (`_wgrad_flush_joint`).  Every row goes through the same K order as in its own
 launch: scores and losses are bit-identical to the two-launch form; parameter gradients are the same sums in another order.
+With dropout on, each pass keeps its own forward-call number and sites: the two output Linears and the LayerNorm backwards behind
+them take one site split at the pass boundary (tnr_gemm_nt_do_split / tnr_ln_bwd_do_split: rows N Lt onwards draw the body
+pass's mask, row index counted from there), embeddings and attention run per pass anyway - every mask is the per-pass form's.
 Student rows live in one table S = [B*(1+K) title rows | B body rows], the layout tnr_kd_embed_loss and
 tnr_score_bwd already use in stage 2 with the body vector in the "user" slot.
 
@@ -156,10 +159,15 @@ class Stage1Engine:
 
     def _joint_ok(self):
         t, b = self.title, self.body
-        ok = bool(self.joint and t.drop is None and b.drop is None and self.cfg_t.pooling == "att" and self.dev.type == "cuda"
-                  and getattr(t, "fcache", None) is None and t.group_wgrad is False)
+        cfg = self.cfg_t
+        same = lambda d: None if d is None else (d["p_hidden"], d["p_attn"], d["seed"])
+        ok = bool(self.joint and same(t.drop) == same(b.drop) and cfg.pooling == "att" and self.dev.type == "cuda"
+                  and getattr(t, "fcache", None) is None and t.group_wgrad is False
+                  # the grouped weight gradients of _wgrad_flush_joint take 256 x 256 tiles only (an inter = 128 * odd config
+                  # runs per pass instead)
+                  and (not self.joint_group_wgrad or (cfg.H % 256 == 0 and cfg.I % 256 == 0)))
         if not ok and getattr(self, "_joint_rows_written", False):
-            # a per-pass step after joint ones (dropout switched on, a tools/ A/B): the title engine's own kernels rely on ZERO rows
+            # a per-pass step after joint ones (a tools/ A/B, `joint` switched off): the title engine's own kernels rely on ZERO rows
             # behind its N Lt rows (the weight gradient reads up to the next multiple of 64), where the joint passes have put body
             # rows - lay the title workspace out afresh, once
             t._alloc_workspace(t.B_alloc)
@@ -192,7 +200,8 @@ class Stage1Engine:
         for e in (t, b):
             if e._rel_stale:
                 e.refresh_rel()
-            e.drop_cur = None
+            e._begin_drop_call()                  # each pass its own forward call, numbered as Engine.encode numbers it
+        dt, db = t._dsite, b._dsite               # the two passes' dropout sites (None: off)
         rows = lambda buf: buf[Mt:M]              # the body pass's rows of a per-token buffer
         self._both(lambda: b._embed_fwd(body_tok, B, bidx, rows(t.x0)),
                    lambda: (teacher_side(), t._embed_fwd(title_tok, N, tidx, t.x0)))
@@ -206,13 +215,15 @@ class Stage1Engine:
             lse_b = b.act[l - b.lo]["lse"] if kept else b.lse
             t.x_in[l] = x
             t._gemm(x, sh["qkv"], a["qkv"], M, bias=t._view(names[3], 3 * H, (3 * H,)), flags=T.EPI_BIAS)
-            self._both(lambda: b._attn_fwd(rows(a["qkv"]), rows(a["ctx"]), lse_b, B, None),
-                       lambda: t._attn_fwd(a["qkv"], a["ctx"], a["lse"] if kept else t.lse, N, None))
-            t._gemm(a["ctx"], sh["o"], a["h1pre"], M, bias=g(names[7]), res=x, flags=T.EPI_BIAS | T.EPI_RES)
+            self._both(lambda: b._attn_fwd(rows(a["qkv"]), rows(a["ctx"]), lse_b, B, db(T.DROP_PROB, l)),
+                       lambda: t._attn_fwd(a["qkv"], a["ctx"], a["lse"] if kept else t.lse, N, dt(T.DROP_PROB, l)))
+            t._gemm(a["ctx"], sh["o"], a["h1pre"], M, bias=g(names[7]), res=x, flags=T.EPI_BIAS | T.EPI_RES,
+                    drop=dt(T.DROP_ATTN_OUT, l), drop_tail=db(T.DROP_ATTN_OUT, l), split_row=Mt)
             t._c("tnr_ln_fwd", a["h1pre"], g(names[8]), g(names[9]), cfg.ln_eps, a["h1"], a["st1"], M, H)
             t._gemm(a["h1"], sh["w1"], a["g"], M, bias=g(names[11]), aux=a["u"] if kept else None,
                     flags=T.EPI_BIAS | T.EPI_GELU | (T.EPI_AUXOUT if kept else 0))
-            t._gemm(a["g"], sh["w2"], a["ypre"], M, bias=g(names[13]), res=a["h1"], flags=T.EPI_BIAS | T.EPI_RES)
+            t._gemm(a["g"], sh["w2"], a["ypre"], M, bias=g(names[13]), res=a["h1"], flags=T.EPI_BIAS | T.EPI_RES,
+                    drop=dt(T.DROP_FFN_OUT, l), drop_tail=db(T.DROP_FFN_OUT, l), split_row=Mt)
             t._c("tnr_ln_fwd", a["ypre"], g(names[14]), g(names[15]), cfg.ln_eps, y, a["st2"], M, H)
             x = y
         t.y_last = x
@@ -231,6 +242,7 @@ class Stage1Engine:
         Mb = B * self.cfg_b.L
         M = Mt + Mb
         g, gr, gi = t.p, t.grads, t.ginv
+        dt, db = t._dsite, b._dsite        # the sites of the two passes' forward calls (drop_cur)
         t._wg = t._wg_defer = None
         rows = lambda buf: buf[Mt:M]
         seqs = lambda buf: buf[N:Ns]
@@ -269,13 +281,22 @@ class Stage1Engine:
             rb = (rb_heads if one else t.red.setdefault((l, "joint", Ns, "ffn"), _ReduceBatch(t.dev))) if tr else None
             P = t.lpart.get(l)
             t._wg = [] if (tr and self.joint_group_wgrad) else None      # the layer's weight gradients collected for one launch
-            t._c("tnr_ln_bwd", dy, a["ypre"], a["st2"], g(names[14]), t.dypre, None, None, None, (P["ln_part"] if tr else None), M, H)
+            # with dropout behind the two output Linears: dx for the residual branch and dx * mask / (1 - p) for the Linear
+            # (Engine.backward_encoder_steps), the masks split at the pass boundary
+            dF, dO = dt(T.DROP_FFN_OUT, l), dt(T.DROP_ATTN_OUT, l)
+            dypre_lin = t.dyprem if dF else t.dypre
+            dh1pre_lin = t.dh1prem if dO else t.dh1pre
+            lnargs = (dy, a["ypre"], a["st2"], g(names[14]), t.dypre, None, None, None, (P["ln_part"] if tr else None), M, H)
+            if dF:
+                t._c("tnr_ln_bwd_do_split", *lnargs, t.dyprem, dF, db(T.DROP_FFN_OUT, l), Mt)
+            else:
+                t._c("tnr_ln_bwd", *lnargs)
             if tr:
                 rb.add(P["ln_part"], nblk, 3 * H, 2 * H, t._view(names[14], 2 * H, (2 * H,), grad=True), 0, gi)
                 rb.add(P["ln_part"][2 * H:], nblk, 3 * H, H, gr[names[13]], 0, gi)
-                t._wgrad(t.dypre, a["g"], gr[names[12]], M)
+                t._wgrad(dypre_lin, a["g"], gr[names[12]], M)
             fused_cs = tr and M > 128            # the column-sum epilogue needs more than one 128-row strip (a toy batch has less)
-            t._gemm(t.dypre, sh["w2T"], t.du, M, aux=a["u"], flags=T.EPI_MULDGELU | (T.EPI_COLSUM if fused_cs else 0),
+            t._gemm(dypre_lin, sh["w2T"], t.du, M, aux=a["u"], flags=T.EPI_MULDGELU | (T.EPI_COLSUM if fused_cs else 0),
                     colsum=P["gcs_part"] if fused_cs else None)
             if tr:
                 if fused_cs:
@@ -291,21 +312,25 @@ class Stage1Engine:
                     after_bucket(bucket)
                     bucket += 1
             t._gemm(t.du, sh["w1T"], t.dh1, M, res=t.dypre, flags=T.EPI_RES)
-            t._c("tnr_ln_bwd", t.dh1, a["h1pre"], a["st1"], g(names[8]), t.dh1pre, None, None, None, (P["ln_part1"] if tr else None), M, H)
+            lnargs = (t.dh1, a["h1pre"], a["st1"], g(names[8]), t.dh1pre, None, None, None, (P["ln_part1"] if tr else None), M, H)
+            if dO:
+                t._c("tnr_ln_bwd_do_split", *lnargs, t.dh1prem, dO, db(T.DROP_ATTN_OUT, l), Mt)
+            else:
+                t._c("tnr_ln_bwd", *lnargs)
             if tr:
                 rba.add(P["ln_part1"], nblk, 3 * H, 2 * H, t._view(names[8], 2 * H, (2 * H,), grad=True), 0, gi)
                 rba.add(P["ln_part1"][2 * H:], nblk, 3 * H, H, gr[names[7]], 0, gi)
-                t._wgrad(t.dh1pre, a["ctx"], gr[names[6]], M)
-            t._gemm(t.dh1pre, sh["oT"], t.dctx, M)
+                t._wgrad(dh1pre_lin, a["ctx"], gr[names[6]], M)
+            t._gemm(dh1pre_lin, sh["oT"], t.dctx, M)
             qp = P["qkvb_part"] if tr else None
 
             def body_attn():
                 if not b._attn_bwd(rows(a["qkv"]), rows(a["ctx"]), b.act[l - b.lo]["lse"], rows(t.dctx), rows(t.dqkv),
-                                   qp[nt_rows:] if tr else None, B, None) and tr:
+                                   qp[nt_rows:] if tr else None, B, db(T.DROP_PROB, l)) and tr:
                     b._c("tnr_colsum", rows(t.dqkv), 3 * H, T.BF16, Mb, 3 * H, qp[nt_rows], b.cs_part, 0)
 
             def title_attn():
-                if not t._attn_bwd(a["qkv"], a["ctx"], a["lse"], t.dctx, t.dqkv, qp, N, None) and tr:
+                if not t._attn_bwd(a["qkv"], a["ctx"], a["lse"], t.dctx, t.dqkv, qp, N, dt(T.DROP_PROB, l)) and tr:
                     t._c("tnr_colsum", t.dqkv, 3 * H, T.BF16, Mt, 3 * H, qp[0], t.cs_part, 0)
             self._both(body_attn, title_attn)
             if tr:

@@ -152,6 +152,7 @@ _SIG = {
     "tnr_reduce_multi": [_P, _I, _P],
     "tnr_dropout_mask": [_D, _L, _L, _P, _P],
     "tnr_dropout_mask_probs": [_D, _L, _I, _I, _P, _P],
+    "tnr_dropout_mask_split": [_D, _D, _L, _L, _L, _P, _P],
     "tnr_scale_inplace": [_P, _L, _F, _P],
     "tnr_amsgrad_step": [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P],
     "tnr_amsgrad_step_guarded": [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P, _c.c_uint, _c.c_uint, _P],
@@ -173,7 +174,10 @@ for _n in ("tnr_embed_ln_fwd", "tnr_embed_ln_fwd_indexed", "tnr_attn_l32_fwd", "
     TYPED.append(_n + "_do")
 _SIG["tnr_gemm_nt_do"] = _SIG["tnr_gemm_nt_ex"][:-1] + [_D, _P]
 _SIG["tnr_ln_bwd_do"] = _SIG["tnr_ln_bwd"][:-1] + [_P, _D, _P]
-TYPED += ["tnr_gemm_nt_do", "tnr_ln_bwd_do"]
+# *_do_split: a second site (the tail rows') and the split row behind the first
+_SIG["tnr_gemm_nt_do_split"] = _SIG["tnr_gemm_nt_do"][:-1] + [_D, _L, _P]
+_SIG["tnr_ln_bwd_do_split"] = _SIG["tnr_ln_bwd_do"][:-1] + [_D, _L, _P]
+TYPED += ["tnr_gemm_nt_do", "tnr_ln_bwd_do", "tnr_gemm_nt_do_split", "tnr_ln_bwd_do_split"]
 for _n in TYPED:
     _SIG[_n + "_f16"] = _SIG[_n]
 _RET = {"tnr_attpool_long_ws_elems": _L, "tnr_attpool_long_ws_elems_f16": _L, "tnr_gemm_tn_ws_elems": _L, "tnr_gemm_tn_ws_elems_f16": _L, "tnr_gemm_colsum_rows_f16": _L, "tnr_gemm_colsum_rows": _L, "tnr_ln_bwd_part_elems": _L, "tnr_ln_bwd_blocks": _L, "tnr_colsum_part_elems": _L,
