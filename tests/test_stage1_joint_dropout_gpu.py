@@ -192,7 +192,7 @@ def test_joint_training_with_dropout_follows_the_per_pass_form():
 
 
 def test_joint_ok_falls_back_when_the_grouped_weight_gradients_cannot_tile():
-    """inter = 128 * odd: _wgrad_flush_joint's 256 x 256 tiles do not fit - the step runs per pass instead of asserting."""
+    """inter = 128 * odd: the shared-round _wgrad_flush's 256 x 256 tiles do not fit - the step runs per pass instead of asserting."""
     eng = Stage1Engine(n_layers=2, trainable_layers=(0, 1), num_teachers=2, npratio=1, title_len=16, body_len=64, device=DEV, batch=2,
                        dtype="fp16", hidden=256, heads=4, inter=384, news_dim=64)
     import hashinit

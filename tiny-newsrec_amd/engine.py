@@ -28,6 +28,25 @@ def _rup(x, m):
     return (x + m - 1) // m * m
 
 
+def _from(buf, r):
+    """Rows r onwards of a workspace buffer (a part's rows: its kernels take their row count as an argument)."""
+    return buf[r:] if r else buf
+
+
+def _fork_join(side, first, second):
+    """first(), then second(); with a stream `side`: first() on it beside second() on the current stream, joined behind."""
+    if side is None:
+        first()
+        second()
+        return
+    main = torch.cuda.current_stream(side.device)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        first()
+    second()
+    main.wait_stream(side)
+
+
 class EngineConfig:
     def __init__(self, n_layers=4, trainable_layers=(2, 3), hidden=768, heads=12, inter=3072, news_dim=256,
                  news_query=200, user_query=200, num_teachers=4, user_log_length=50, npratio=4, num_words=30,
@@ -579,7 +598,7 @@ class Engine:
         # partial sums of the bias / LayerNorm gradients: a set per trainable layer, so that ONE batched reduction at the end of the
         # backward can sum them all (they are a few tens of MB per layer)
         self.lpart = {l: dict(ln_part=f(T.query("tnr_ln_bwd_part_elems", Mp, H)), ln_part1=f(T.query("tnr_ln_bwd_part_elems", Mp, H)),
-                              gcs_part=f(T.query("tnr_gemm_colsum_rows", Mp), I), qkvb_part=f(Nx, 3 * H), cs_tmp=f(I), cs_tmp2=f(3 * H))
+                              gcs_part=f(T.query("tnr_gemm_colsum_rows", Mp), I), qkvb_part=f(Nx, 3 * H), cs_tmp=f(I))
                       for l in cfg.trainable_layers}
         self.red = {}                                                      # gradient bucket -> _ReduceBatch
         self.cs_part = f(max(T.query("tnr_colsum_part_elems", Mp, 3 * H if L > 32 else QPAD),
@@ -624,7 +643,7 @@ class Engine:
 
     # ------------------------------------------------------------------ kernel wrappers
     def _gemm(self, a, w, c, M, bias=None, res=None, aux=None, flags=0, colsum=None, drop=None, drop_tail=None, split_row=None):
-        """drop_tail / split_row: rows [split_row, M) under the site drop_tail (tnr_gemm_nt_do_split; stage 1's joint passes)."""
+        """drop_tail / split_row: rows [split_row, M) under the site drop_tail (tnr_gemm_nt_do_split; a second part's rows)."""
         N, K = w.shape
         args = (a, a.stride(0), w, w.stride(0), c, c.stride(0), M, N, K, bias, res,
                 res.stride(0) if res is not None else 0, aux, aux.stride(0) if aux is not None else 0, flags, colsum)
@@ -646,17 +665,23 @@ class Engine:
         self._c("tnr_gemm_tn_wgrad_ex", dy, dy.stride(0), x, x.stride(0), dw, dw.stride(0), M, N, K, self.ws,
                self._wgrad_splits(N, K)[0], acc, self.ginv)
 
-    def _wgrad_flush(self):
+    def _wgrad_flush(self, shared_round=False):
         """The weight gradients collected since the last flush in ONE persistent launch (+ one slab-sum launch): their (split, tile)
         units share a queue, so the workgroups that finish one gradient's units go on with the next one's instead of idling to the
         launch boundary, and a workgroup kept off its CU by another stream's kernel costs a unit of up to four rounds' worth
-        instead of a whole round.  Each gradient is computed exactly as by its own launch (slabs of its own in self.ws)."""
+        instead of a whole round.  Each gradient is computed exactly as by its own launch (slabs of its own in self.ws).
+        shared_round (stage 1's joint passes: few rows, 8 896 at 30 / 128): a full round of units per gradient (_wgrad_splits) would
+        mean 20 m steps per unit, 7 fp32 slabs and a slab sum per gradient - instead ALL the collected gradients (at most four, of
+        256 x 256 tiles) share ONE round: the same number of splits each, so every unit runs the same number of m steps."""
         pend, self._wg = self._wg, []
         if not pend:
             return
+        if shared_round:
+            assert len(pend) <= 4 and all(N % 256 == 0 and K % 256 == 0 for _, _, _, _, N, K, _ in pend)
+            shared = max(1, min(64, (256 * Engine.WGRAD_UNITS) // sum((N // 256) * (K // 256) for _, _, _, _, N, K, _ in pend)))
         probs, off = [], 0
         for dy, x, dw, M, N, K, acc in pend:
-            splits, elems = self._wgrad_splits(N, K)
+            splits, elems = (shared, T.query("tnr_gemm_tn_ws_elems", N, K, shared)) if shared_round else self._wgrad_splits(N, K)
             probs.append(dict(dY=dy, lddy=dy.stride(0), X=x, ldx=x.stride(0), dW=dw, lddw=dw.stride(0), M=M, N=N, K=K,
                               ws=self.ws[off:off + elems], splits=splits, accumulate=acc, out_scale=self.ginv))
             off += _rup(elems, 64)
@@ -747,8 +772,19 @@ class Engine:
             self._pos_cache = (key, pid)
         return pid
 
-    # pieces of encode() / backward_encoder_steps() that depend on the sequence length, with their per-token operands explicit
-    # (stage 1's joint passes run them per pass on row ranges of buffers both passes share, stage1.py)
+    # encode() and backward_encoder_steps() work on a list of PARTS laid one behind the other in this engine's per-token buffers:
+    # (engine, sequences, first token row, first sequence row).  One pass is one part, [(self, n_seq, 0, 0)]; stage 1's joint passes
+    # are two, the body engine's behind the title engine's, with the title engine as host (stage1.py).  Every Linear, LayerNorm and
+    # weight gradient is one launch over all parts' rows; what depends on the sequence length - the pieces below, with their
+    # per-token operands explicit - runs once per part on that part's rows, through the part's engine (its L, masks, statistics).
+    def _per_part(self, parts, side, fn):
+        """fn(engine, sequences, first row, first sequence) per part.  Two parts: the one behind first (stage 1 encodes the bodies
+        first), on the stream `side` beside the other if there is one."""
+        if len(parts) == 1:
+            fn(*parts[0])
+        else:
+            _fork_join(side, lambda: fn(*parts[1]), lambda: fn(*parts[0]))
+
     def _embed_fwd(self, tok, n_seq, nidx, x0):
         cfg, g, ds = self.cfg, self.p, self._dsite
         L, H = cfg.L, cfg.H
@@ -804,19 +840,31 @@ class Engine:
         self._c("tnr_attn_long_bwd_do", *bargs, dPb) if dPb else self._c("tnr_attn_long_bwd", *bargs)
         return False
 
-    def encode(self, tok, n_seq, nidx=None, out=None, stop_at=None, train=True, extra=None):
+    def encode(self, tok, n_seq, nidx=None, out=None, stop_at=None, train=True, extra=None, parts=None, src2=None, side=None,
+               before=None):
         """NewsEncoder.forward model_bert.py:119-137 -> news vectors S[:n_seq] (fp32).
         tok (n_seq, 2L) int64 on device, or (nidx given) tok = resident news_combined (n+1, 2L) int32 and
-        nidx (n_seq,) int32 news indices.  stop_at = l: return the hidden states entering layer l instead."""
+        nidx (n_seq,) int32 news indices.  stop_at = l: return the hidden states entering layer l instead.
+        parts (two, this engine's first: see _per_part): the second part's sequences, src2 = its (tok, nidx), go through the same
+        launches behind this one's, their news vectors to S[n_seq:]; side = the stream of its own kernels or None; before() is
+        called directly in front of this part's embedding launch (work of the caller's that runs beside the part behind)."""
         cfg = self.cfg
-        H, L = cfg.H, cfg.L
-        M = n_seq * L
+        H = cfg.H
+        parts = parts or [(self, n_seq, 0, 0)]
+        two = len(parts) > 1
+        M0 = n_seq * cfg.L                                    # rows of the first part: where a second one's begin
+        M = sum(n * e.cfg.L for e, n, _, _ in parts)
+        Ns = sum(n for _, n, _, _ in parts)
+        assert M <= self.Mp and Ns <= self.nv.shape[0]
         g = self.p
-        if self._rel_stale:
-            self.refresh_rel()
-        self._begin_drop_call(train)
+        for e, _, _, _ in parts:
+            if e._rel_stale:
+                e.refresh_rel()
+            e._begin_drop_call(train)                         # each part its own numbered forward call
         ds = self._dsite
+        ds2 = parts[1][0]._dsite if two else None             # ... and the second part's, for the rows from M0 on (_gemm)
         fc = getattr(self, "fcache", None) if self.drop_cur is None else None      # a cached prefix has no fresh masks
+        assert not two or (fc is None and stop_at is None and out is None and not extra and cfg.pooling == "att")
         first = 0
         if fc is not None and nidx is not None and stop_at is None and tok.data_ptr() == fc[2]:
             # frozen prefix from the per-news cache (build_frozen_cache): two row gathers replace embedding + lo layers
@@ -824,7 +872,14 @@ class Engine:
             T.call("tnr_gather_rows", fc[1], fc[3], nidx, n_seq, self.Lr, 1, self.mask_add, n_seq, 0)
             first = self.lo
         else:
-            self._embed_fwd(tok, n_seq, nidx, self.x0)
+            def embed(e, n, r0, s0):
+                if r0:
+                    e._embed_fwd(src2[0], n, src2[1], self.x0[r0:])
+                    return
+                if before:
+                    before()
+                e._embed_fwd(tok, n, nidx, self.x0)
+            self._per_part(parts, side, embed)
         x = self.x0
         self.x_in = {}
         for l in range(first, cfg.n_layers):
@@ -838,31 +893,35 @@ class Engine:
             bqkv = self._view(names[3], 3 * H, (3 * H,))
             self.x_in[l] = x
             self._gemm(x, sh["qkv"], a["qkv"], M, bias=bqkv, flags=T.EPI_BIAS)
-            self._attn_fwd(a["qkv"], a["ctx"], a["lse"] if kept else self.lse, n_seq, ds(T.DROP_PROB, l))
+
+            def attn(e, n, r0, s0):
+                e._attn_fwd(_from(a["qkv"], r0), _from(a["ctx"], r0), e.act[l - e.lo]["lse"] if kept else e.lse, n,
+                            e._dsite(T.DROP_PROB, l))
+            self._per_part(parts, side, attn)
             self._gemm(a["ctx"], sh["o"], a["h1pre"], M, bias=g(names[7]), res=x, flags=T.EPI_BIAS | T.EPI_RES,
-                       drop=ds(T.DROP_ATTN_OUT, l))
+                       drop=ds(T.DROP_ATTN_OUT, l), drop_tail=ds2(T.DROP_ATTN_OUT, l) if two else None, split_row=M0)
             self._c("tnr_ln_fwd", a["h1pre"], g(names[8]), g(names[9]), cfg.ln_eps, a["h1"], a["st1"], M, H)
             fl = T.EPI_BIAS | T.EPI_GELU | (T.EPI_AUXOUT if kept else 0)
             self._gemm(a["h1"], sh["w1"], a["g"], M, bias=g(names[11]), aux=a["u"] if kept else None, flags=fl)
             self._gemm(a["g"], sh["w2"], a["ypre"], M, bias=g(names[13]), res=a["h1"], flags=T.EPI_BIAS | T.EPI_RES,
-                       drop=ds(T.DROP_FFN_OUT, l))
+                       drop=ds(T.DROP_FFN_OUT, l), drop_tail=ds2(T.DROP_FFN_OUT, l) if two else None, split_row=M0)
             self._c("tnr_ln_fwd", a["ypre"], g(names[14]), g(names[15]), cfg.ln_eps, y, a["st2"], M, H)
             x = y
         self.y_last = x
         # pooling (model_bert.py:130-135: AttentionPooling without mask | token 0 | mean) + dense (:136)
         if cfg.pooling == "att":
             self._gemm(x, self.sh_a1, self.e, M, bias=self.b_a1, flags=T.EPI_BIAS | T.EPI_TANH | T.EPI_OUTF32)
-            self._attpool_fwd(x, self.e, self.nv, n_seq)
+            self._per_part(parts, side, lambda e, n, r0, s0: e._attpool_fwd(_from(x, r0), _from(self.e, r0), _from(self.nv, s0), n))
         else:
-            self._c("tnr_pool_fwd", x, self.nv, n_seq, L, H, int(cfg.pooling == "mean"))
+            self._c("tnr_pool_fwd", x, self.nv, n_seq, cfg.L, H, int(cfg.pooling == "mean"))
         wd = g(PFX + "dense.weight")
         dst = self.S if out is None else out
-        dense = (self.nv, H, 1, 0, wd, H, 1, 0, dst, cfg.D, 0, g(PFX + "dense.bias"), 0, n_seq, cfg.D, H)
+        dense = (self.nv, H, 1, 0, wd, H, 1, 0, dst, cfg.D, 0, g(PFX + "dense.bias"), 0, Ns, cfg.D, H)
         if extra:      # independent fp32 GEMMs the caller had pending (the teachers' projection): one launch with the dense layer
             self._sgemm_group([self._sgemm_problem(*dense)] + list(extra))
         else:
             self._sgemm(*dense)
-        return dst[:n_seq]
+        return dst[:Ns]
 
     # ------------------------------------------------------------------ forward-only paths
     @torch.no_grad()
@@ -1129,43 +1188,69 @@ class Engine:
         for i in range(T_):
             rb.add(self.dP[i], Rt, D, D, dbt[i])
 
-    def backward_encoder(self, dvec, N, acc=0, after_bucket=None, pend=None):
+    def backward_encoder(self, dvec, N, acc=0, after_bucket=None, pend=None, **two_parts):
         """NewsEncoder backward for the N sequences of the last encode(): dvec (N,D) fp32 = d loss / d news vectors.
         acc=1 adds to the gradients already in flat_g (second pass over the same parameters, stage 1).
-        pend: fp32 GEMM problems of the caller that depend on nothing computed here; they ride in the first grouped launch."""
-        for _ in self.backward_encoder_steps(dvec, N, acc, after_bucket, pend=pend):
+        pend: fp32 GEMM problems of the caller that depend on nothing computed here; they ride in the first grouped launch.
+        two_parts: parts, side, group_wgrad of backward_encoder_steps."""
+        for _ in self.backward_encoder_steps(dvec, N, acc, after_bucket, pend=pend, **two_parts):
             pass
 
-    def backward_encoder_steps(self, dvec, N, acc=0, after_bucket=None, defer=False, split_ffn=False, pend=None):
+    def _ln_bwd(self, lnargs, dx_masked, drop, drop_tail, split_row):
+        """LayerNorm backward behind a Linear with output dropout `drop`: dx for the residual branch and dx_masked = dx * mask /
+        (1 - p), the Linear's output gradient (drop None: off, dx is both).  drop_tail / split_row as in _gemm."""
+        if drop is None:
+            self._c("tnr_ln_bwd", *lnargs)
+        elif drop_tail is not None:
+            self._c("tnr_ln_bwd_do_split", *lnargs, dx_masked, drop, drop_tail, split_row)
+        else:
+            self._c("tnr_ln_bwd_do", *lnargs, dx_masked, drop)
+
+    def backward_encoder_steps(self, dvec, N, acc=0, after_bucket=None, defer=False, split_ffn=False, pend=None, parts=None, side=None,
+                               group_wgrad=None):
         """backward_encoder as a generator.  defer=True (stage 1): the weight gradients are not launched but collected in
         self._wg_defer, and the generator yields wherever they have to be on their way - after the pooling head, after every
         trainable layer (and, split_ffn, after its FFN block: the point a gradient bucket completes) - so that a caller running
-        two passes over the same parameters in step can launch both passes' contributions to a weight as ONE chained problem."""
+        two passes over the same parameters in step can launch both passes' contributions to a weight as ONE chained problem.
+        parts, side: as in the encode() this backward belongs to; dvec then holds both parts' rows.  Two parts always write
+        (acc = 0, no defer), collect a layer's weight gradients if group_wgrad (None: self.group_wgrad) and launch them with one
+        round shared by all of them (_wgrad_flush)."""
         cfg = self.cfg
         self._red_check()
+        parts = parts or [(self, N, 0, 0)]
+        two = len(parts) > 1
+        assert not two or (acc == 0 and not defer and cfg.pooling == "att")
         self._wg_defer = [] if defer else None
-        L, D, H, I = cfg.L, cfg.D, cfg.H, cfg.I
-        M = N * L
+        D, H, I = cfg.D, cfg.H, cfg.I
+        M0 = N * cfg.L                      # rows of the first part: where a second one's begin
+        M = sum(n * e.cfg.L for e, n, _, _ in parts)
+        Ns = sum(n for _, n, _, _ in parts)
+        group = (self.group_wgrad if group_wgrad is None else group_wgrad) and not defer
         g, gr = self.p, self.grads
         self._wg = None                    # nothing collected from an earlier, interrupted backward
         ds = self._dsite                   # sites of the forward call this backward belongs to (self.drop_cur)
+        ds2 = parts[1][0]._dsite if two else None      # ... and of the second part's, for the rows from M0 on
         gi = self.ginv                     # parameter gradients below the pooling backward: 1 / loss scale on the way out
         # no bucket hook (one GPU): every partial sum of the backward in ONE batched reduction at its end
         one = after_bucket is None and self.merge_reductions
-        rb = rb_heads = self.red.setdefault(("heads", acc, N, one), _ReduceBatch(self.dev))
+        # the recorded reduction tables of one pass (writing or adding) and of two parts never replay each other's
+        form = "joint" if two else acc
+        rb = rb_heads = self.red.setdefault(("heads", form, Ns, one), _ReduceBatch(self.dev))
         # dense + pooling of the news encoder
         wd = g(PFX + "dense.weight")
         self._sgemm_group(list(pend or []) + [
-            self._sgemm_problem(dvec, 1, D, 0, self.nv, 1, H, 0, gr[PFX + "dense.weight"], H, 0, None, 0, D, H, N, ksplit=self.KS,
+            self._sgemm_problem(dvec, 1, D, 0, self.nv, 1, H, 0, gr[PFX + "dense.weight"], H, 0, None, 0, D, H, Ns, ksplit=self.KS,
                                 beta=float(acc)),
-            self._sgemm_problem(dvec, D, 1, 0, wd, 1, H, 0, self.dnv, H, 0, None, 0, N, H, D, alpha=self.gscale)])   # loss scale enters here
-        rb.add(dvec, N, D, D, gr[PFX + "dense.bias"], acc)       # column sums; in place, behind the two GEMMs that read dvec
+            self._sgemm_problem(dvec, D, 1, 0, wd, 1, H, 0, self.dnv, H, 0, None, 0, Ns, H, D, alpha=self.gscale)])   # loss scale enters here
+        rb.add(dvec, Ns, D, D, gr[PFX + "dense.bias"], acc)       # column sums; in place, behind the two GEMMs that read dvec
         y = self.y_last
         if cfg.pooling == "att":
-            self._attpool_bwd(y, self.e, self.dnv, self.dy2, self.dpre, self.dw2p, self.db2p, self.db1p, N)
-            rb.add(self.dw2p, N, cfg.Qn, cfg.Qn, gr[PFX + "attn.att_fc2.weight"], acc, gi)
-            rb.add(self.db2p, N, 1, 1, gr[PFX + "attn.att_fc2.bias"], acc, gi)
-            rb.add(self.db1p, N, QPAD, QPAD, self._view(PFX + "attn.att_fc1.bias", QPAD, (QPAD,), grad=True), acc, gi)
+            self._per_part(parts, side, lambda e, n, r0, s0: e._attpool_bwd(
+                _from(y, r0), _from(self.e, r0), _from(self.dnv, s0), _from(self.dy2, r0), _from(self.dpre, r0), _from(self.dw2p, s0),
+                _from(self.db2p, s0), _from(self.db1p, s0), n))
+            rb.add(self.dw2p, Ns, cfg.Qn, cfg.Qn, gr[PFX + "attn.att_fc2.weight"], acc, gi)
+            rb.add(self.db2p, Ns, 1, 1, gr[PFX + "attn.att_fc2.bias"], acc, gi)
+            rb.add(self.db1p, Ns, QPAD, QPAD, self._view(PFX + "attn.att_fc1.bias", QPAD, (QPAD,), grad=True), acc, gi)
         if not one or not cfg.trainable_layers:
             rb.flush()
         if cfg.pooling == "att":
@@ -1180,9 +1265,13 @@ class Engine:
         if cfg.pooling == "att":
             self._gemm(self.dpre, self.sh_a1T, self.dy, M, res=self.dy2, flags=T.EPI_RES)
         else:
-            self._c("tnr_pool_bwd", self.dnv, self.dy, N, L, H, int(cfg.pooling == "mean"))
+            self._c("tnr_pool_bwd", self.dnv, self.dy, N, cfg.L, H, int(cfg.pooling == "mean"))
         dy = self.dy
         bucket = 1
+        nblk = T.query("tnr_ln_bwd_blocks", M)
+        # q / k / v bias: the short-sequence attention backward leaves one partial row per sequence, the long one none (its dqkv
+        # columns are summed into ONE row): the parts' rows one behind the other in qkvb_part, one reduction job over all of them
+        qrows = [n if e.cfg.L <= 32 else 1 for e, n, _, _ in parts]
         for l in range(cfg.n_layers - 1, self.lo - 1, -1):
             names, sh, a = layer_param_order(l), self.sh[l], self.act[l - self.lo]
             tr = l in cfg.trainable_layers
@@ -1194,23 +1283,22 @@ class Engine:
             # (attention block of layer lo) is then a third of a layer instead of a whole one
             # (without a bucket hook - one GPU - nothing waits for any bucket: the partial sums of all layers and of the heads go
             # into one batched reduction at the end of the backward)
-            self._wg = [] if (tr and self.group_wgrad and not defer) else None
-            rba = (rb_heads if one else self.red.setdefault((l, acc, N, "att"), _ReduceBatch(self.dev))) if tr else None
-            rb = (rb_heads if one else self.red.setdefault((l, acc, N, "ffn"), _ReduceBatch(self.dev))) if tr else None
+            self._wg = [] if (tr and group) else None
+            rba = (rb_heads if one else self.red.setdefault((l, form, Ns, "att"), _ReduceBatch(self.dev))) if tr else None
+            rb = (rb_heads if one else self.red.setdefault((l, form, Ns, "ffn"), _ReduceBatch(self.dev))) if tr else None
             P = self.lpart.get(l)
-            nblk = T.query("tnr_ln_bwd_blocks", M)
             # with dropout behind the two output Linears the LayerNorm backward has two outputs: dx for the residual branch and
             # dx * mask / (1 - p) = the Linear's output gradient (its weight gradient, dgrad and -- through the partials -- bias)
-            dF, dO, dPb = ds(T.DROP_FFN_OUT, l), ds(T.DROP_ATTN_OUT, l), ds(T.DROP_PROB, l)
+            dF, dO = ds(T.DROP_FFN_OUT, l), ds(T.DROP_ATTN_OUT, l)
             dypre_lin = self.dyprem if dF else self.dypre
             dh1pre_lin = self.dh1prem if dO else self.dh1pre
-            lnargs = (dy, a["ypre"], a["st2"], g(names[14]), self.dypre, None, None, None, (P["ln_part"] if tr else None), M, H)
-            self._c("tnr_ln_bwd_do", *lnargs, self.dyprem, dF) if dF else self._c("tnr_ln_bwd", *lnargs)
+            self._ln_bwd((dy, a["ypre"], a["st2"], g(names[14]), self.dypre, None, None, None, (P["ln_part"] if tr else None), M, H),
+                         dypre_lin, dF, ds2(T.DROP_FFN_OUT, l) if two else None, M0)
             if tr:
                 rb.add(P["ln_part"], nblk, 3 * H, 2 * H, self._view(names[14], 2 * H, (2 * H,), grad=True), acc, gi)   # [dgamma | dbeta]
                 rb.add(P["ln_part"][2 * H:], nblk, 3 * H, H, gr[names[13]], acc, gi)                                 # output.dense.bias
                 self._wgrad(dypre_lin, a["g"], gr[names[12]], M, acc)
-            fused_cs = tr and M > 128            # the column-sum epilogue needs more than one 128-row strip
+            fused_cs = tr and M > 128            # the column-sum epilogue needs more than one 128-row strip (a toy batch has less)
             self._gemm(dypre_lin, sh["w2T"], self.du, M, aux=a["u"], flags=T.EPI_MULDGELU | (T.EPI_COLSUM if fused_cs else 0),
                        colsum=P["gcs_part"] if fused_cs else None)
             if tr:
@@ -1226,27 +1314,31 @@ class Engine:
                     yield (l, "ffn")
                 if after_bucket:
                     if self._wg is not None:
-                        self._wgrad_flush()            # the FFN block's two gradients: its bucket goes out now
+                        self._wgrad_flush(two)         # the FFN block's two gradients: its bucket goes out now
                     after_bucket(bucket)
                     bucket += 1
             self._gemm(self.du, sh["w1T"], self.dh1, M, res=self.dypre, flags=T.EPI_RES)
-            lnargs = (self.dh1, a["h1pre"], a["st1"], g(names[8]), self.dh1pre, None, None, None, (P["ln_part1"] if tr else None), M, H)
-            self._c("tnr_ln_bwd_do", *lnargs, self.dh1prem, dO) if dO else self._c("tnr_ln_bwd", *lnargs)
+            self._ln_bwd((self.dh1, a["h1pre"], a["st1"], g(names[8]), self.dh1pre, None, None, None, (P["ln_part1"] if tr else None), M, H),
+                         dh1pre_lin, dO, ds2(T.DROP_ATTN_OUT, l) if two else None, M0)
             if tr:
                 rba.add(P["ln_part1"], nblk, 3 * H, 2 * H, self._view(names[8], 2 * H, (2 * H,), grad=True), acc, gi)
                 rba.add(P["ln_part1"][2 * H:], nblk, 3 * H, H, gr[names[7]], acc, gi)                               # attention.output.dense.bias
                 self._wgrad(dh1pre_lin, a["ctx"], gr[names[6]], M, acc)
             self._gemm(dh1pre_lin, sh["oT"], self.dctx, M)
-            if self._attn_bwd(a["qkv"], a["ctx"], a["lse"], self.dctx, self.dqkv, (P["qkvb_part"] if tr else None), N, dPb):
-                if tr:
-                    rba.add(P["qkvb_part"], N, 3 * H, 3 * H, self._view(names[3], 3 * H, (3 * H,), grad=True), acc, gi)
-            elif tr:
-                self._c("tnr_colsum", self.dqkv, 3 * H, T.BF16, M, 3 * H, P["cs_tmp2"][:3 * H], self.cs_part, 0)
-                rba.add(P["cs_tmp2"], 1, 3 * H, 3 * H, self._view(names[3], 3 * H, (3 * H,), grad=True), acc, gi)
+            qp = P["qkvb_part"] if tr else None
+
+            def attn(e, n, r0, s0):
+                q0 = qrows[0] if r0 else 0             # the part's first row of qkvb_part
+                dqkv = _from(self.dqkv, r0)
+                if not e._attn_bwd(_from(a["qkv"], r0), _from(a["ctx"], r0), e.act[l - e.lo]["lse"], _from(self.dctx, r0), dqkv,
+                                   _from(qp, q0) if tr else None, n, e._dsite(T.DROP_PROB, l)) and tr:
+                    e._c("tnr_colsum", dqkv, 3 * H, T.BF16, n * e.cfg.L, 3 * H, qp[q0], e.cs_part, 0)
+            self._per_part(parts, side, attn)
             if tr:
+                rba.add(qp, sum(qrows), 3 * H, 3 * H, self._view(names[3], 3 * H, (3 * H,), grad=True), acc, gi)
                 self._wgrad(self.dqkv, x_in, self._view(names[0], 3 * H * H, (3 * H, H), grad=True), M, acc)
                 if self._wg is not None:               # all four of the layer (two under a bucket hook), before the next layer overwrites their operands
-                    self._wgrad_flush()
+                    self._wgrad_flush(two)
                     self._wg = None
                 if defer:
                     yield (l, "att")

@@ -18,7 +18,11 @@ rows one by one, so the body pass's rows are laid directly BEHIND the title pass
 ONE launch over M = N Lt + B Lb rows instead of one per pass (8 896 rows at 30 / 128, 24 064 at 24 / 512: tile orders large enough
 for the persistent 256-wide kernels); only what depends on the sequence length - embeddings, attention, pooling - still runs per
 pass, on its row range (one stream: `joint_streams` puts the body's on a second one, measured slower).  A layer's four weight
-gradients leave in ONE grouped persistent launch whose units share one round (`_wgrad_flush_joint`).  Every row goes through the same K order as in its own
+gradients leave in ONE grouped persistent launch whose units share one round (Engine._wgrad_flush, shared_round).  There is no layer
+loop here: Engine.encode and Engine.backward_encoder_steps work on a list of parts of the host engine's buffers, one for a single
+pass, and this class only hands them two - [(title, N, 0, 0), (body, B, N Lt, N)], the title engine as host (`_parts`).  The per-pass
+forms (`joint` off, or a configuration `_joint_ok` refuses) call the same two functions once per engine.
+Every row goes through the same K order as in its own
 launch: scores and losses are bit-identical to the two-launch form; parameter gradients are the same sums in another order.
 With dropout on, each pass keeps its own forward-call number and sites: the two output Linears and the LayerNorm backwards behind
 them take one site split at the pass boundary (tnr_gemm_nt_do_split / tnr_ln_bwd_do_split: rows N Lt onwards draw the body
@@ -35,7 +39,7 @@ csrc/dropout.h; the title and the body pass draw independent masks, as two passe
 import torch
 
 import tnr_hip as T
-from engine import BERT, PFX, QPAD, Engine, EngineConfig, _ReduceBatch, layer_param_order
+from engine import Engine, EngineConfig, _ReduceBatch, _fork_join
 
 
 class Stage1Engine:
@@ -78,18 +82,14 @@ class Stage1Engine:
         body_table (n, 2Lb) int32 token tables and teacher tables (T, n, D) fp32 stay in HBM; idx (B, 1+K) int32 holds the
         positive document first, then its sampled negatives (the body is the positive's).  body_idx (B,) int32 contiguous = idx[:, 0]
         if the loader has it (saves the step its one strided copy)."""
-        t, b = self.title, self.body
-        cfg = self.cfg_t
-        B = idx.shape[0]
-        C, D, T_ = cfg.C, cfg.D, cfg.T
-        assert idx.shape[1] == C
-        self._prepare(B)
-        self.ran_joint = self._joint_ok()      # (before anything is copied into the workspaces: it may lay them out afresh)
-        N, Rt = B * C, B * C + B
-        self.cur = (B, N, Rt)
-        t.label = label.to(torch.int64).contiguous()
+        t = self.title
+        B, T_ = idx.shape[0], self.cfg_t.T
+        assert idx.shape[1] == self.cfg_t.C
+        N, Rt = self._begin(B, label)
+        D = self.cfg_t.D
         tidx = idx.reshape(-1).to(torch.int32).contiguous()
         bidx = idx[:, 0].to(torch.int32).contiguous() if body_idx is None else body_idx
+
         def teacher_side():
             # the teacher side (row gathers, teacher scores, projections) needs nothing of the student's: in front of the title pass,
             # where it runs beside the start of the body pass instead of alone between the encoders and the losses
@@ -97,15 +97,7 @@ class Stage1Engine:
                 T.call("tnr_gather_rows", t_title_tables, t_title_tables.shape[1], tidx, N, D, T_, t.X, t.X.shape[1], 0)
                 T.call("tnr_gather_rows", t_body_tables, t_body_tables.shape[1], bidx, B, D, T_, t.X, t.X.shape[1], N)
                 self._teacher_side(B, N, Rt)
-
-        def title_pass():
-            teacher_side()
-            t.encode(title_table, N, nidx=tidx)
-        if self.ran_joint:
-            self._encode_joint(B, N, title_table, tidx, body_table, bidx, teacher_side)
-        else:
-            self._encode_both(lambda: b.encode(body_table, B, nidx=bidx, out=t.S[N:]), title_pass)
-        return self._heads(B, N, Rt)
+        return self._encode_heads(B, N, Rt, title_table, tidx, body_table, bidx, teacher_side)
 
     def forward(self, title, body, label, teacher_titles, teacher_bodies):
         """title (B,1+K,2Lt) / body (B,2Lb) int64 [ids | mask]; label (B,); teacher_* lists of (B,1+K,D) / (B,D) fp32
@@ -115,11 +107,7 @@ class Stage1Engine:
         B = title.shape[0]
         C, D, T_ = cfg.C, cfg.D, cfg.T
         assert title.shape[1:] == (C, 2 * cfg.L) and body.shape == (B, 2 * self.cfg_b.L)
-        self._prepare(B)
-        self.ran_joint = self._joint_ok()      # (before anything is copied into the workspaces: it may lay them out afresh)
-        N, Rt = B * C, B * C + B
-        self.cur = (B, N, Rt)
-        t.label = label.to(torch.int64).contiguous()
+        N, Rt = self._begin(B, label)
         b.tok[:B].copy_(body)
         t.tok[:N].copy_(title.reshape(N, 2 * cfg.L))
         for i in range(T_):
@@ -129,14 +117,35 @@ class Stage1Engine:
         def teacher_side():
             if T_:
                 self._teacher_side(B, N, Rt)
+        return self._encode_heads(B, N, Rt, t.tok[:N], None, b.tok[:B], None, teacher_side)
 
-        def title_pass():
-            teacher_side()
-            t.encode(t.tok[:N], N)
+    def _begin(self, B, label):
+        """Workspaces for a batch of B, the form this step takes (ran_joint) and its label -> (title sequences, student rows)."""
+        self._prepare(B)
+        self.ran_joint = self._joint_ok()      # (before anything is copied into the workspaces: it may lay them out afresh)
+        N = B * self.cfg_t.C
+        self.cur = (B, N, N + B)
+        self.title.label = label.to(torch.int64).contiguous()
+        return N, N + B
+
+    def _parts(self, B, N):
+        """The joint passes as parts of the title engine's buffers (engine.py, _per_part): the bodies' rows behind the titles'."""
+        return [(self.title, N, 0, 0), (self.body, B, N * self.cfg_t.L, N)]
+
+    def _stream_if(self, on):
+        return self._side_stream() if (on and self.dev.type == "cuda") else None
+
+    def _encode_heads(self, B, N, Rt, title_tok, tidx, body_tok, bidx, teacher_side):
+        """Both encoder passes (the bodies first: cell 12), news vectors -> S[:N] (titles), S[N:N + B] (bodies); then the heads."""
+        t, b = self.title, self.body
         if self.ran_joint:
-            self._encode_joint(B, N, t.tok[:N], None, b.tok[:B], None, teacher_side)
+            t.encode(title_tok, N, nidx=tidx, parts=self._parts(B, N), src2=(body_tok, bidx), side=self._stream_if(self.joint_streams),
+                     before=teacher_side)
         else:
-            self._encode_both(lambda: b.encode(b.tok[:B], B, out=t.S[N:]), title_pass)    # cell 12 encodes the bodies first
+            def title_pass():
+                teacher_side()
+                t.encode(title_tok, N, nidx=tidx)
+            _fork_join(self._stream_if(self.two_streams), lambda: b.encode(body_tok, B, nidx=bidx, out=t.S[N:]), title_pass)
         return self._heads(B, N, Rt)
 
     # The body pass on a second stream beside the title pass: most launches of either pass are partial rounds (4 800 / 4 096 token
@@ -156,6 +165,7 @@ class Stage1Engine:
     joint_streams = False   # True: the body's per-pass kernels (embeddings, attention, pooling) on the second stream beside the title's.
                             # Measured (interleaved legs, one box): 1.816 -> 1.718 ms at 30 / 128 and 3.830 -> 3.717 at 24 / 512 WITHOUT it -
                             # ten fork / join pairs per step cost more than running two short kernels side by side wins
+    joint_group_wgrad = True    # the joint passes' weight gradients of a layer in ONE persistent launch + one slab sum
 
     def _joint_ok(self):
         t, b = self.title, self.body
@@ -163,8 +173,8 @@ class Stage1Engine:
         same = lambda d: None if d is None else (d["p_hidden"], d["p_attn"], d["seed"])
         ok = bool(self.joint and same(t.drop) == same(b.drop) and cfg.pooling == "att" and self.dev.type == "cuda"
                   and getattr(t, "fcache", None) is None and t.group_wgrad is False
-                  # the grouped weight gradients of _wgrad_flush_joint take 256 x 256 tiles only (an inter = 128 * odd config
-                  # runs per pass instead)
+                  # the grouped weight gradients that share one round (Engine._wgrad_flush) take 256 x 256 tiles only (an
+                  # inter = 128 * odd config runs per pass instead)
                   and (not self.joint_group_wgrad or (cfg.H % 256 == 0 and cfg.I % 256 == 0)))
         if not ok and getattr(self, "_joint_rows_written", False):
             # a per-pass step after joint ones (a tools/ A/B, `joint` switched off): the title engine's own kernels rely on ZERO rows
@@ -173,218 +183,6 @@ class Stage1Engine:
             t._alloc_workspace(t.B_alloc)
         self._joint_rows_written = ok
         return ok
-
-    def _both(self, body_fn, title_fn):
-        """The two passes' own kernels of one stage of the joint passes: side by side on two streams, joined behind."""
-        if not self.joint_streams:
-            body_fn()
-            title_fn()
-            return
-        main, side = torch.cuda.current_stream(self.dev), self._side_stream()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            body_fn()
-        title_fn()
-        main.wait_stream(side)
-
-    def _encode_joint(self, B, N, title_tok, tidx, body_tok, bidx, teacher_side):
-        """Engine.encode for both passes at once (model_bert.py:119-137 twice): token rows [0, N Lt) are the titles', [N Lt, N Lt +
-        B Lb) the bodies'; news vectors -> S[:N] (titles), S[N:N + B] (bodies)."""
-        t, b = self.title, self.body
-        cfg = self.cfg_t
-        H, D = cfg.H, cfg.D
-        Mt = N * cfg.L
-        M = Mt + B * self.cfg_b.L
-        assert M <= t.Mp and N + B <= t.nv.shape[0]
-        g = t.p
-        for e in (t, b):
-            if e._rel_stale:
-                e.refresh_rel()
-            e._begin_drop_call()                  # each pass its own forward call, numbered as Engine.encode numbers it
-        dt, db = t._dsite, b._dsite               # the two passes' dropout sites (None: off)
-        rows = lambda buf: buf[Mt:M]              # the body pass's rows of a per-token buffer
-        self._both(lambda: b._embed_fwd(body_tok, B, bidx, rows(t.x0)),
-                   lambda: (teacher_side(), t._embed_fwd(title_tok, N, tidx, t.x0)))
-        x = t.x0
-        t.x_in = {}
-        for l in range(cfg.n_layers):
-            names, sh = layer_param_order(l), t.sh[l]
-            kept = l >= t.lo
-            a = t.act[l - t.lo] if kept else t.scr
-            y = a["y"] if kept else t.scr_y[l & 1]
-            lse_b = b.act[l - b.lo]["lse"] if kept else b.lse
-            t.x_in[l] = x
-            t._gemm(x, sh["qkv"], a["qkv"], M, bias=t._view(names[3], 3 * H, (3 * H,)), flags=T.EPI_BIAS)
-            self._both(lambda: b._attn_fwd(rows(a["qkv"]), rows(a["ctx"]), lse_b, B, db(T.DROP_PROB, l)),
-                       lambda: t._attn_fwd(a["qkv"], a["ctx"], a["lse"] if kept else t.lse, N, dt(T.DROP_PROB, l)))
-            t._gemm(a["ctx"], sh["o"], a["h1pre"], M, bias=g(names[7]), res=x, flags=T.EPI_BIAS | T.EPI_RES,
-                    drop=dt(T.DROP_ATTN_OUT, l), drop_tail=db(T.DROP_ATTN_OUT, l), split_row=Mt)
-            t._c("tnr_ln_fwd", a["h1pre"], g(names[8]), g(names[9]), cfg.ln_eps, a["h1"], a["st1"], M, H)
-            t._gemm(a["h1"], sh["w1"], a["g"], M, bias=g(names[11]), aux=a["u"] if kept else None,
-                    flags=T.EPI_BIAS | T.EPI_GELU | (T.EPI_AUXOUT if kept else 0))
-            t._gemm(a["g"], sh["w2"], a["ypre"], M, bias=g(names[13]), res=a["h1"], flags=T.EPI_BIAS | T.EPI_RES,
-                    drop=dt(T.DROP_FFN_OUT, l), drop_tail=db(T.DROP_FFN_OUT, l), split_row=Mt)
-            t._c("tnr_ln_fwd", a["ypre"], g(names[14]), g(names[15]), cfg.ln_eps, y, a["st2"], M, H)
-            x = y
-        t.y_last = x
-        t._gemm(x, t.sh_a1, t.e, M, bias=t.b_a1, flags=T.EPI_BIAS | T.EPI_TANH | T.EPI_OUTF32)
-        self._both(lambda: b._attpool_fwd(rows(x), rows(t.e), t.nv[N:N + B], B),
-                   lambda: t._attpool_fwd(x, t.e, t.nv, N))
-        t._sgemm(t.nv, H, 1, 0, g(PFX + "dense.weight"), H, 1, 0, t.S, D, 0, g(PFX + "dense.bias"), 0, N + B, D, H)
-
-    def _backward_joint(self, dS, B, N, after_bucket, pend, rb_heads, one):
-        """Engine.backward_encoder_steps for both passes at once: dS[:N + B] = d loss / d news vectors, titles then bodies."""
-        t, b = self.title, self.body
-        cfg = self.cfg_t
-        D, H, I = cfg.D, cfg.H, cfg.I
-        Ns = N + B
-        Mt = N * cfg.L
-        Mb = B * self.cfg_b.L
-        M = Mt + Mb
-        g, gr, gi = t.p, t.grads, t.ginv
-        dt, db = t._dsite, b._dsite        # the sites of the two passes' forward calls (drop_cur)
-        t._wg = t._wg_defer = None
-        rows = lambda buf: buf[Mt:M]
-        seqs = lambda buf: buf[N:Ns]
-        rb = rb_heads
-        dvec = dS[:Ns]
-        t._sgemm_group(list(pend or []) + [
-            t._sgemm_problem(dvec, 1, D, 0, t.nv, 1, H, 0, gr[PFX + "dense.weight"], H, 0, None, 0, D, H, Ns, ksplit=t.KS),
-            t._sgemm_problem(dvec, D, 1, 0, g(PFX + "dense.weight"), 1, H, 0, t.dnv, H, 0, None, 0, Ns, H, D, alpha=t.gscale)])
-        rb.add(dvec, Ns, D, D, gr[PFX + "dense.bias"])
-        y = t.y_last
-        self._both(lambda: b._attpool_bwd(rows(y), rows(t.e), seqs(t.dnv), rows(t.dy2), rows(t.dpre), seqs(t.dw2p), seqs(t.db2p),
-                                          seqs(t.db1p), B),
-                   lambda: t._attpool_bwd(y, t.e, t.dnv, t.dy2, t.dpre, t.dw2p, t.db2p, t.db1p, N))
-        rb.add(t.dw2p, Ns, cfg.Qn, cfg.Qn, gr[PFX + "attn.att_fc2.weight"], 0, gi)
-        rb.add(t.db2p, Ns, 1, 1, gr[PFX + "attn.att_fc2.bias"], 0, gi)
-        rb.add(t.db1p, Ns, QPAD, QPAD, t._view(PFX + "attn.att_fc1.bias", QPAD, (QPAD,), grad=True), 0, gi)
-        if not one or not cfg.trainable_layers:
-            rb.flush()
-        t._wgrad(t.dpre, y, t._view(PFX + "attn.att_fc1.weight", QPAD * H, (QPAD, H), grad=True), M)
-        if after_bucket:
-            after_bucket(0)
-        if not cfg.trainable_layers:
-            return
-        t._gemm(t.dpre, t.sh_a1T, t.dy, M, res=t.dy2, flags=T.EPI_RES)
-        dy = t.dy
-        bucket = 1
-        nblk = T.query("tnr_ln_bwd_blocks", M)
-        # q / k / v bias: the short-sequence attention backward leaves one partial row per sequence, the long one none (its dqkv
-        # columns are summed into ONE row): both passes' partial rows in one buffer, one reduction job
-        nt_rows, nb_rows = (N if cfg.L <= 32 else 1), (B if self.cfg_b.L <= 32 else 1)
-        for l in range(cfg.n_layers - 1, t.lo - 1, -1):
-            names, sh, a = layer_param_order(l), t.sh[l], t.act[l - t.lo]
-            tr = l in cfg.trainable_layers
-            x_in = t.x_in[l]
-            rba = (rb_heads if one else t.red.setdefault((l, "joint", Ns, "att"), _ReduceBatch(t.dev))) if tr else None
-            rb = (rb_heads if one else t.red.setdefault((l, "joint", Ns, "ffn"), _ReduceBatch(t.dev))) if tr else None
-            P = t.lpart.get(l)
-            t._wg = [] if (tr and self.joint_group_wgrad) else None      # the layer's weight gradients collected for one launch
-            # with dropout behind the two output Linears: dx for the residual branch and dx * mask / (1 - p) for the Linear
-            # (Engine.backward_encoder_steps), the masks split at the pass boundary
-            dF, dO = dt(T.DROP_FFN_OUT, l), dt(T.DROP_ATTN_OUT, l)
-            dypre_lin = t.dyprem if dF else t.dypre
-            dh1pre_lin = t.dh1prem if dO else t.dh1pre
-            lnargs = (dy, a["ypre"], a["st2"], g(names[14]), t.dypre, None, None, None, (P["ln_part"] if tr else None), M, H)
-            if dF:
-                t._c("tnr_ln_bwd_do_split", *lnargs, t.dyprem, dF, db(T.DROP_FFN_OUT, l), Mt)
-            else:
-                t._c("tnr_ln_bwd", *lnargs)
-            if tr:
-                rb.add(P["ln_part"], nblk, 3 * H, 2 * H, t._view(names[14], 2 * H, (2 * H,), grad=True), 0, gi)
-                rb.add(P["ln_part"][2 * H:], nblk, 3 * H, H, gr[names[13]], 0, gi)
-                t._wgrad(dypre_lin, a["g"], gr[names[12]], M)
-            fused_cs = tr and M > 128            # the column-sum epilogue needs more than one 128-row strip (a toy batch has less)
-            t._gemm(dypre_lin, sh["w2T"], t.du, M, aux=a["u"], flags=T.EPI_MULDGELU | (T.EPI_COLSUM if fused_cs else 0),
-                    colsum=P["gcs_part"] if fused_cs else None)
-            if tr:
-                if fused_cs:
-                    rb.add(P["gcs_part"], t._q("tnr_gemm_colsum_rows", M), I, I, gr[names[11]], 0, gi)
-                else:
-                    t._c("tnr_colsum", t.du, I, T.BF16, M, I, P["cs_tmp"][:I], t.cs_part, 0)
-                    rb.add(P["cs_tmp"], 1, I, I, gr[names[11]], 0, gi)
-                t._wgrad(t.du, a["h1"], gr[names[10]], M)
-                if not one:
-                    rb.flush()
-                if after_bucket:
-                    self._wgrad_flush_joint()          # the FFN block's two gradients: its bucket goes out now
-                    after_bucket(bucket)
-                    bucket += 1
-            t._gemm(t.du, sh["w1T"], t.dh1, M, res=t.dypre, flags=T.EPI_RES)
-            lnargs = (t.dh1, a["h1pre"], a["st1"], g(names[8]), t.dh1pre, None, None, None, (P["ln_part1"] if tr else None), M, H)
-            if dO:
-                t._c("tnr_ln_bwd_do_split", *lnargs, t.dh1prem, dO, db(T.DROP_ATTN_OUT, l), Mt)
-            else:
-                t._c("tnr_ln_bwd", *lnargs)
-            if tr:
-                rba.add(P["ln_part1"], nblk, 3 * H, 2 * H, t._view(names[8], 2 * H, (2 * H,), grad=True), 0, gi)
-                rba.add(P["ln_part1"][2 * H:], nblk, 3 * H, H, gr[names[7]], 0, gi)
-                t._wgrad(dh1pre_lin, a["ctx"], gr[names[6]], M)
-            t._gemm(dh1pre_lin, sh["oT"], t.dctx, M)
-            qp = P["qkvb_part"] if tr else None
-
-            def body_attn():
-                if not b._attn_bwd(rows(a["qkv"]), rows(a["ctx"]), b.act[l - b.lo]["lse"], rows(t.dctx), rows(t.dqkv),
-                                   qp[nt_rows:] if tr else None, B, db(T.DROP_PROB, l)) and tr:
-                    b._c("tnr_colsum", rows(t.dqkv), 3 * H, T.BF16, Mb, 3 * H, qp[nt_rows], b.cs_part, 0)
-
-            def title_attn():
-                if not t._attn_bwd(a["qkv"], a["ctx"], a["lse"], t.dctx, t.dqkv, qp, N, dt(T.DROP_PROB, l)) and tr:
-                    t._c("tnr_colsum", t.dqkv, 3 * H, T.BF16, Mt, 3 * H, qp[0], t.cs_part, 0)
-            self._both(body_attn, title_attn)
-            if tr:
-                rba.add(qp, nt_rows + nb_rows, 3 * H, 3 * H, t._view(names[3], 3 * H, (3 * H,), grad=True), 0, gi)
-                t._wgrad(t.dqkv, x_in, t._view(names[0], 3 * H * H, (3 * H, H), grad=True), M)
-                self._wgrad_flush_joint()              # before the next layer overwrites their operands
-                if not one:
-                    rba.flush()
-            if l > t.lo:
-                nxt = t.dy2 if dy is t.dy else t.dy
-                t._gemm(t.dqkv, sh["qkvT"], nxt, M, res=t.dh1pre, flags=T.EPI_RES)
-                dy = nxt
-            if tr and after_bucket:
-                after_bucket(bucket)
-                bucket += 1
-        t._wg = None
-        if one:
-            rb_heads.flush()
-
-    joint_group_wgrad = True    # the joint passes' weight gradients of a layer in ONE persistent launch + one slab sum
-
-    def _wgrad_flush_joint(self):
-        """The weight gradients collected since the last flush (a layer's four; two and two under a bucket hook) as one
-        tnr_gemm_tn_wgrad_group launch.  The joint passes have few rows (8 896 at 30 / 128): a launch per gradient with a full
-        round of (split, tile) units each (Engine._wgrad_splits) means 20 m steps per unit, 7 fp32 slabs per gradient and a slab
-        sum per gradient; here ALL the collected gradients share one round - every gradient gets the same number of splits, so
-        every unit runs the same number of m steps - and one slab sum."""
-        t = self.title
-        pend, t._wg = t._wg, ([] if t._wg is not None else None)
-        if not pend:
-            return
-        tiles = sum((N // 256) * (K // 256) for _, _, _, _, N, K, _ in pend)
-        assert all(N % 256 == 0 and K % 256 == 0 for _, _, _, _, N, K, _ in pend)
-        splits = max(1, min(64, (256 * Engine.WGRAD_UNITS) // tiles))
-        probs, off = [], 0
-        for dy, x, dw, M, N, K, acc in pend:
-            elems = T.query("tnr_gemm_tn_ws_elems", N, K, splits)
-            probs.append(dict(dY=dy, lddy=dy.stride(0), X=x, ldx=x.stride(0), dW=dw, lddw=dw.stride(0), M=M, N=N, K=K,
-                              ws=t.ws[off:off + elems], splits=splits, accumulate=acc, out_scale=t.ginv))
-            off += (elems + 63) // 64 * 64
-        assert off <= t.ws.numel() and len(probs) <= 4
-        T.wgrad_group(probs, f16=t.f16)
-
-    def _encode_both(self, body_pass, title_pass):
-        if not self.two_streams or self.dev.type != "cuda":
-            body_pass()
-            title_pass()
-            return
-        main, side = torch.cuda.current_stream(self.dev), self._side_stream()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            body_pass()
-        title_pass()
-        main.wait_stream(side)
 
     def _side_stream(self):
         if getattr(self, "_side", None) is None:
@@ -451,7 +249,9 @@ class Stage1Engine:
             if self.cfg_t.T:
                 t._transform_grads(Rt, rbh, pend)
             T.call("tnr_score_bwd", S, t.cidx, S[N:], t.dscore, dS, dS[N:], B, C, D)
-            self._backward_joint(dS, B, N, after_bucket, pend, rbh, one)
+            # always writes; a layer's weight gradients leave in one grouped launch whose units share one round (Engine._wgrad_flush)
+            t.backward_encoder(dS[:Rt], N, after_bucket=after_bucket, pend=pend, parts=self._parts(B, N),
+                               side=self._stream_if(self.joint_streams), group_wgrad=self.joint_group_wgrad)
             return
         one_t = t.merge_reductions and not (self.chain_wgrad and after_bucket is not None)
         if self.cfg_t.T:
