@@ -455,7 +455,7 @@ int tnr_cast_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
 /* ---- fp16 activations ------------------------------------------------------------------------------
  * Every entry point that touches 16-bit tensors exists a second time with the suffix _f16: identical
  * signature and semantics with IEEE half instead of bf16 (same MFMA rate, 3 more mantissa bits: the build used
- * for the 1e-3 parity bound).  The sources are compiled twice (-DTNR_BUILD_F16). */
+ * for the 1e-3 parity bound).  The sources that touch the 16-bit type are compiled twice (-DTNR_BUILD_F16). */
 int tnr_embed_ln_fwd_f16(const int64_t* tok, int64_t n_seq, int L, int H, const float* word, const float* pos,
                      const float* type0, const float* gamma, const float* beta, float eps,
                      void* out, float* mask_add, void* stream);

@@ -36,6 +36,17 @@ def test_library_never_switches_or_drains_a_device():
     assert os.path.exists(hooks) and hasattr(ctypes.CDLL(hooks), "tnr_debug_cu_hog")
 
 
+def test_build_switch_is_tested_in_common_h_only():
+    """Which sources are built twice (bf16 and -DTNR_BUILD_F16) is a fact of the Makefile's TYPED / ONCE lists: no source fences
+    part of itself off for one of the two builds, csrc/common.h alone maps the switch to the 16-bit type and the entry-point names."""
+    import glob
+    csrc = os.path.join(ROOT, "tiny-newsrec_amd", "csrc")
+    files = sorted(f for ext in ("*.hip", "*.cpp", "*.h") for f in glob.glob(os.path.join(csrc, ext)))
+    assert len(files) >= 10 and os.path.join(csrc, "common.h") in files
+    users = [os.path.basename(f) for f in files if "TNR_BUILD_F16" in open(f).read()]
+    assert users == ["common.h"], users
+
+
 def test_version_without_gpu():
     assert T.query("tnr_version") == 1
 
@@ -59,7 +70,7 @@ def _plan(M, N, flags=0, n_cu=256):
 
 
 def test_gemm_row_tiling_covers_every_row_exactly_once():
-    """Host logic of the persistent NT kernel (csrc/gemm.hip:pp_plan / pp_panel): P row panels, x of them 32*mi rows and the rest
+    """Host logic of the persistent NT kernel (csrc/gemm_plan.hip:pp_plan, csrc/gemm.hip:pp_panel): P row panels, x of them 32*mi rows and the rest
     32 rows shorter, spread evenly.  The panels must tile [0, >= M) without gaps or overlaps for every shape, and the column
     sums' partial rows are counted per 256-row panel (tnr_gemm_colsum_rows), so a COLSUM launch keeps the uniform tiling."""
     import random

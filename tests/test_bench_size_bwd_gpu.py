@@ -1,6 +1,6 @@
 """GPU parity of the NON-GEMM kernels of the backward AT THE HEADLINE STEP'S SIZE, against the numpy oracle.
 
-The row kernels switch block shape with the row count (norm_embed.hip: lnb_rows / cs_rows change at M = 32 768) and the
+The row kernels switch block shape with the row count (csrc/common.h: lnb_rows / cs_rows change at M = 32 768) and the
 small-case tests (tests/test_kernels_gpu.py: M <= 1234, N <= 9 sequences) never reach the branch bench.py runs at
 B = 32 (M = 52 800 token rows, n_seq = 1 760, A = 12).  Here every such kernel runs at that size AND on both sides of the
 32 767 / 32 768 boundary, in both 16-bit builds, called exactly the way engine.py calls it (partials + tnr_reduce_multi),

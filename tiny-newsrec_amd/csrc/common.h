@@ -7,9 +7,10 @@
 
 #include "../../include/tnr_hip.h"
 
-// The 16-bit activation type.  The sources are compiled twice: once with bf16 (entry points tnr_*) and once
-// with -DTNR_F16 (IEEE half, entry points tnr_*_f16, same MFMA rate, 3 more mantissa bits).  The identifier
-// `bf16` below means "the 16-bit type of this build".
+// The 16-bit activation type.  The typed sources (TYPED in the Makefile) are compiled twice: once with bf16 (entry points
+// tnr_*) and once with -DTNR_BUILD_F16 (IEEE half, entry points tnr_*_f16, same MFMA rate, 3 more mantissa bits).  The
+// identifier `bf16` below means "the 16-bit type of this build".  Everything else (ONCE in the Makefile) is fp32 or host code
+// and is built once; this header is the only place that tests the switch.
 #ifdef TNR_BUILD_F16
 typedef _Float16 bf16;
 #define TNR_NAME(x) x##_f16
@@ -50,9 +51,6 @@ struct TnrGemmOpts {
     int clock_n;
 };
 TnrGemmOpts* tnr_gemm_opts();
-// The tile-queue counter set of (current device, stream) for the persistent GEMM kernels of BOTH builds (defined once, in the
-// bf16 build of gemm.hip); reset = zero it again (stream-ordered).  NULL + tnr_last_error when the table is full.
-unsigned* tnr_pp_queue_of(void* stream, bool reset);
 
 // Runs `body` once per device of this process (function attributes such as the dynamic LDS limit are set per device); two
 // threads racing through it both run the idempotent body.
@@ -171,3 +169,80 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 __device__ __forceinline__ bf16x4 ds_read_tr16(const void* lds_ptr) {
     return __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)lds_ptr));
 }
+
+// ---- shared between the typed sources (built twice) and the once-built ones ---------------------------------------------
+// A typed launcher that needs an fp32 kernel calls the once-built side through one of the `*_launch` helpers below: they launch
+// and nothing else, the caller checks (TNR_CHECK_LAUNCH) under its own name.
+
+// LayerNorm backward (norm_embed.hip; workspace sizes: util_f32.hip)
+constexpr int LNB_ROWS = 128;  // rows per block (8 half waves x 16 rows); short inputs use 32 so that every CU gets work
+static inline int lnb_rows(int64_t M) { return M >= 32768 ? LNB_ROWS : 32; }
+static inline int64_t lnb_blocks(int64_t M) { return (M + lnb_rows(M) - 1) / lnb_rows(M); }
+
+// column sums: block = 256 columns (64 threads x 4) x 4 row lanes over `rows_per_block` rows: 512 for tall inputs, 64 for short
+// ones (a 1792-row input on 512-row blocks was 4 workgroups walking 128 dependent loads each: 33 us for 1.8 MB)
+constexpr int CS_ROWS = 512;
+static inline int cs_rows(int64_t M) { return M >= 32768 ? CS_ROWS : 64; }
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ Xb, int64_t ldx, int64_t M, int64_t N,
+                                                     float* __restrict__ partb, int64_t sX, int64_t sPart, int rows_per_block) {
+    const T* X = Xb + (int64_t)blockIdx.z * sX;
+    float* part = partb + (int64_t)blockIdx.z * sPart;
+    // thread handles 4 consecutive columns; 64 threads across 256 columns, 4 row groups
+    __shared__ float red[4][256];
+    const int cg = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * 256 + cg * 4;
+    const int64_t m0 = (int64_t)blockIdx.y * rows_per_block;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c < N) {
+        int64_t mend = m0 + rows_per_block < M ? m0 + rows_per_block : M;
+        for (int64_t m = m0 + rg; m < mend; m += 4) {
+            if constexpr (sizeof(T) == 2) {
+                bf16x4 a = *(const bf16x4*)((const bf16*)X + m * ldx + c);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s[r] += (float)a[r];
+            } else {
+                f32x4 a = *(const f32x4*)((const float*)X + m * ldx + c);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s[r] += a[r];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[rg][cg * 4 + r] = s[r];
+    __syncthreads();
+    int t = threadIdx.x;
+    int64_t col = (int64_t)blockIdx.x * 256 + t;
+    if (col < N) part[(int64_t)blockIdx.y * gridDim.z * N + col] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+}
+}  // namespace
+void colsum_f32_launch(dim3 grid, const float* X, int64_t ldx, int64_t M, int64_t N, float* part, int64_t sX, int rows_per_block,
+                       hipStream_t st);                                   // colsum_kernel<float>: util_f32.hip
+
+// attention pooling of few, long sequences (attpool.hip): tokens per chunk, and the stages without 16-bit data (heads.hip)
+constexpr int AP_CH = 64;
+void attpool_long_score_launch(const float* e, int64_t lde, const float* w2, const float* b2, int Q, float* alpha, int64_t n_tok,
+                               int L, hipStream_t st);
+void attpool_long_fwd_fin_launch(const float* ws, float* alpha, float* nv, float* den, int64_t n_seq, int L, int H, hipStream_t st);
+void attpool_long_bwd_fin_launch(const float* part, int Q, int64_t lddpre, int nch, float* dw2_part, float* db2_part,
+                                 float* db1_part, int64_t n_seq, hipStream_t st);
+
+// GEMM host state and planning (gemm_plan.hip), one copy for both builds of gemm.hip.
+// A tile-queue counter set: 8 tile counters + the count of workgroups that have left, each on a 256-byte line of its own.
+constexpr int PP_Q_STRIDE = 64;
+constexpr int PP_Q_SET = 9 * PP_Q_STRIDE;
+constexpr int PP_QUEUE_SETS = 128;
+// The counter set of (current device, stream); reset = zero it again (stream-ordered).  NULL + tnr_last_error when the table is full.
+unsigned* tnr_pp_queue_of(void* stream, bool reset);
+int device_cus();                                                          // option `cus`, or the current device's
+struct PpPlan { int mi, P, x; };                                           // instance (32 mi rows), row panels, tall ones among them
+PpPlan pp_plan(int64_t M, int64_t N, int flags, int n_cu);
+int nt_route(int64_t M, int64_t N, int64_t K, int flags, int n_cu);        // TNR_ROUTE_*
+constexpr int TN_MAXP = 4;                                                 // weight gradients per grouped launch
+// unit ranges of the eight XCD labels, xb[9], from ubase[TN_MAXP + 1] (first unit of each problem, then the total) and tiles_per_split[n]
+void tn_group_ranges(const int* ubase, const int* tiles_per_split, int n, int* xb);
+// one slab sum: out[N, K] (ld ldo) (+)= out_scale * sum of `splits` slabs of NK = N * K floats at ws (NK == 0: nothing to do)
+struct SlabSum { const float* ws; float* out; int64_t NK, ldo; int splits, K, accumulate; float out_scale; };
+void slab_reduce_launch(const SlabSum& s, hipStream_t st);
+void slab_reduce_group_launch(const SlabSum* s, int n, hipStream_t st);    // n <= TN_MAXP sums in one launch

@@ -10,7 +10,6 @@
 // next tile's loads issued before the current tile's MFMAs, one barrier per K tile; 64 KB LDS per
 // workgroup -> 2 workgroups per CU overlap each other's barrier stalls.
 #include <algorithm>
-#include <mutex>
 #include <type_traits>
 
 #include "common.h"
@@ -310,40 +309,12 @@ struct TNArgs {
 // Up to four weight gradients in ONE persistent launch (tnr_gemm_tn_wgrad_group): the (split, tile) units of the problems are
 // numbered one after the other (ubase[i] = first unit of problem i; entries from n on hold the total) and pulled from the same
 // queue.  Each unit is computed exactly as in the problem's own launch.
-constexpr int TN_MAXP = 4;
 struct TNGroup {
     TNArgs p[TN_MAXP];
     int ubase[TN_MAXP + 1];
     int xb[9];                 // unit range of XCD label x: [xb[x], xb[x + 1]) - equal shares of the WORK (units differ in length between problems)
     unsigned* queue;
 };
-// the eight ranges: one problem -> equal unit counts (the old rule); several -> cut where the cumulated m steps (+ a fixed cost per
-// unit for its prologue and slab store) reach x / 8 of the total
-static void tn_group_ranges(TNGroup& g, int n) {
-    const int total = g.ubase[TN_MAXP];
-    if (n == 1) {
-        const int q8 = total >> 3, r8 = total & 7;
-        for (int x = 0; x <= 8; ++x) g.xb[x] = x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8;
-        return;
-    }
-    int64_t w[TN_MAXP], cum[TN_MAXP + 1];
-    cum[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        w[i] = g.p[i].tiles_per_split + 8;
-        cum[i + 1] = cum[i] + w[i] * (g.ubase[i + 1] - g.ubase[i]);
-    }
-    g.xb[0] = 0;
-    g.xb[8] = total;
-    for (int x = 1; x < 8; ++x) {
-        const int64_t t = cum[n] * x / 8;
-        int i = 0;
-        while (i + 1 < n && cum[i + 1] <= t) ++i;
-        int u = g.ubase[i] + (int)((t - cum[i] + w[i] / 2) / w[i]);
-        if (u < g.xb[x - 1]) u = g.xb[x - 1];
-        if (u > total) u = total;
-        g.xb[x] = u;
-    }
-}
 
 __device__ __forceinline__ int tn_swz(int row) { return (((row & 3) | (((row >> 3) & 1) << 2)) << 1); }
 
@@ -896,8 +867,6 @@ __device__ __forceinline__ int pp_bswz(int row) { return ((row >> 1) & 1) | (((r
 // wait would read the register before the data is there.
 // (a counter set: 8 tile counters + the count of workgroups that have left, each on a 256-byte line of its own - the workgroups
 // of one XCD label then update a line that stays in their L2 instead of passing it between the eight)
-constexpr int PP_Q_STRIDE = 64;
-[[maybe_unused]] constexpr int PP_Q_SET = 9 * PP_Q_STRIDE;
 __device__ __forceinline__ void pp_q_fetch(unsigned& dst, unsigned* ctr, bool on) {
     const unsigned long long m = (unsigned)__builtin_amdgcn_readfirstlane(on ? 1 : 0);
     unsigned long long sv;
@@ -1395,55 +1364,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_rs_kernel(TNGroup grp) {
     leave();
 }
 
-__global__ void slab_reduce_kernel(const float* __restrict__ ws, int splits, int64_t NK, int K, float* out,
-                                   int64_t ldo, int accumulate, float out_scale) {
-    int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i4 >= NK) return;
-    f32x4 s = *(const f32x4*)(ws + i4);
-    for (int z = 1; z < splits; ++z) s += *(const f32x4*)(ws + (int64_t)z * NK + i4);
-    int64_t n = i4 / K, k = i4 - n * K;
-    float* o = out + n * ldo + k;
-    s *= out_scale;
-    if (accumulate) s += *(const f32x4*)o;
-    *(f32x4*)o = s;
-}
-
-// the slab sums of up to four problems in one launch (blockIdx.y = problem): each element exactly as slab_reduce_kernel does it
-struct SlabGroup {
-    const float* ws[TN_MAXP]; float* out[TN_MAXP]; int64_t NK[TN_MAXP], ldo[TN_MAXP];
-    int splits[TN_MAXP], K[TN_MAXP], accumulate[TN_MAXP]; float out_scale[TN_MAXP];
-};
-__global__ void slab_reduce_group_kernel(SlabGroup g) {
-    const int pi = blockIdx.y;
-    const float* ws = g.ws[0]; float* out = g.out[0]; int64_t NK = g.NK[0], ldo = g.ldo[0];
-    int splits = g.splits[0], K = g.K[0], accumulate = g.accumulate[0]; float out_scale = g.out_scale[0];
-#pragma unroll
-    for (int k = 1; k < TN_MAXP; ++k)
-        if (pi == k) {
-            ws = g.ws[k]; out = g.out[k]; NK = g.NK[k]; ldo = g.ldo[k];
-            splits = g.splits[k]; K = g.K[k]; accumulate = g.accumulate[k]; out_scale = g.out_scale[k];
-        }
-    int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i4 >= NK) return;
-    f32x4 s = *(const f32x4*)(ws + i4);
-    for (int z = 1; z < splits; ++z) s += *(const f32x4*)(ws + (int64_t)z * NK + i4);
-    int64_t n = i4 / K, k = i4 - n * K;
-    float* o = out + n * ldo + k;
-    s *= out_scale;
-    if (accumulate) s += *(const f32x4*)o;
-    *(f32x4*)o = s;
-}
-
 }  // namespace
-
-extern "C" int TNR_NAME(tnr_gemm_nt_do)(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
-                              int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
-                              void* aux, int64_t ldaux, int flags, float* colsum_part, const tnr_dropout_t* drop,
-                              void* stream);
-extern "C" int TNR_NAME(tnr_gemm_nt_do_split)(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
-                                    int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
-                                    void* aux, int64_t ldaux, int flags, float* colsum_part, const tnr_dropout_t* drop,
-                                    const tnr_dropout_t* drop_tail, int64_t split_row, void* stream);
 
 extern "C" int TNR_NAME(tnr_gemm_nt)(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                            int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
@@ -1453,138 +1374,15 @@ extern "C" int TNR_NAME(tnr_gemm_nt)(const void* A, int64_t lda, const void* B, 
 
 extern "C" int64_t TNR_NAME(tnr_gemm_colsum_rows)(int64_t M) { return ((M + 255) / 256) * 4; }
 
-// ---- routing ---------------------------------------------------------------------------------------
-// Which kernel a launch takes depends on the shape only (and on the process-wide options of api.cpp, which tools set
-// through tnr_gemm_set_option -- the library never reads the environment).  tnr_gemm_nt_route() exposes the decision
-// so that the parity tests can pin every route.
-static int device_cus() {
-    if (tnr_gemm_opts()->cus > 0) return tnr_gemm_opts()->cus;
-    static int cus[64] = {0};
-    int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return 256;
-    if (cus[devid] == 0) {
-        hipDeviceProp_t prop;
-        int n = 256;
-        if (hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.multiProcessorCount > 0) n = prop.multiProcessorCount;
-        cus[devid] = n;
-    }
-    return cus[devid];
-}
-
-// Tiling of a ping-pong launch: instance (MI = 8: panels of 256 / 224 rows, MI = 7: 224 / 192), P row panels, x of them tall
-// (pp_panel).  Cost model: a tile costs its rows + a fixed 24 (prologue latency, bias, queue), every XCD label's 1/8 of the tiles
-// is pulled by 1/8 of the workgroups, a mixed launch pays half the height difference for the luck of the draw; candidates
-// are all P between "all tall" and "all short".  mix = 0 (option `mix`, or column sums riding along: their partial rows
-// are counted per 256-row panel, tnr_gemm_colsum_rows): the uniform tiling with the old 224 / 256 rule.
-struct PpPlan { int mi, P, x; };
-static PpPlan pp_plan(int64_t M, int64_t N, int flags, int n_cu) {
-    const TnrGemmOpts& o = *tnr_gemm_opts();
-    const int64_t ncol = N / 256;
-    if ((flags & TNR_EPI_COLSUM) || !o.mix) {
-        const int64_t t256 = ((M + 255) / 256) * ncol, t224 = ((M + 223) / 224) * ncol;
-        const int64_t c256 = ((t256 + n_cu - 1) / n_cu) * 256, c224 = ((t224 + n_cu - 1) / n_cu) * 224;
-        bool use224 = c224 * 108 < c256 * 100 && !(flags & TNR_EPI_COLSUM);   // per-tile fixed costs: need a clear win
-        if (o.bm) use224 = o.bm == 224 && !(flags & TNR_EPI_COLSUM);
-        const int P = (int)(use224 ? (M + 223) / 224 : (M + 255) / 256);
-        return PpPlan{use224 ? 7 : 8, P, P};
-    }
-    PpPlan best{8, (int)((M + 255) / 256), (int)((M + 255) / 256)};
-    double best_span = 1e30;
-    const int64_t W = n_cu >= 8 ? n_cu / 8 : 1;
-    for (int mi = 8; mi >= 7; --mi) {
-        if (o.bm && o.bm != 32 * mi) continue;
-        const int tall = 32 * mi, shrt = tall - 32;
-        const int64_t pmin = (M + tall - 1) / tall, pmax = (M + shrt - 1) / shrt;
-        for (int64_t p = pmin; p <= pmax; ++p) {
-            int64_t x = M - p * shrt;
-            x = x > 0 ? (x + 31) / 32 : 0;                          // tall panels needed to cover M rows
-            const double ct = tall + 24.0, cs = shrt + 24.0, f = (double)x / (double)p, cbar = f * ct + (1.0 - f) * cs;
-            const int64_t n = (p * ncol + 7) / 8, k = n / W, r = n % W;
-            double span = (double)k * cbar + (r ? cbar : 0.0) + (x > 0 && x < p ? 0.5 * (ct - cs) : 0.0);
-            if (k == 0) span = x > 0 ? ct : cs;
-            if (span < best_span - 1e-9) { best_span = span; best = PpPlan{mi, (int)p, (int)x}; }
-        }
-    }
-    return best;
-}
-
-static int nt_route(int64_t M, int64_t N, int64_t K, int flags, int n_cu) {
-    const TnrGemmOpts& o = *tnr_gemm_opts();
-    // 256x256 tiles: the persistent kernel, for N % 256 == 0 unless option "pp" = 0 rules out its tile queue
-    const bool t256 = (N % 256) == 0 && o.pp;
-    // short inputs (stage-1 title / body passes, small eval batches): when the 256x256 grid would leave more than 40 % of
-    // the CUs without a tile, the 128x128 kernel (2 workgroups per CU) spreads the same work four times finer
-    const bool sparse256 = t256 && ((M + 255) / 256) * (N / 256) * 100 < (int64_t)n_cu * o.fine_pct && !(flags & TNR_EPI_COLSUM);
-    const bool odd_gelu = !t256 && (flags & (TNR_EPI_GELU | TNR_EPI_MULDGELU));   // the 256x128 kernel has no table GELU
-    if (o.ver == 1 || M <= 128 || odd_gelu || (sparse256 && o.allow_fine)) return TNR_ROUTE_128x128;
-    if (o.ver == 2 || !t256) return TNR_ROUTE_256x128;
-    return pp_plan(M, N, flags, n_cu).mi == 7 ? TNR_ROUTE_224x256 : TNR_ROUTE_256x256;
-}
-
 // the epilogue flag combinations of engine.py get an instance each with the flags at compile time (forward: QKV / pooled query,
 // attention output + FFN down, FFN up with and without the pre-activation side output, pooling fc1 ; backward: the four dgrads)
 #define TNR_PP_FLAG_SETS(X)                                                                                              \
     X(0) X(TNR_EPI_BIAS) X(TNR_EPI_RES) X(TNR_EPI_BIAS | TNR_EPI_RES) X(TNR_EPI_BIAS | TNR_EPI_GELU)                      \
     X(TNR_EPI_BIAS | TNR_EPI_GELU | TNR_EPI_AUXOUT) X(TNR_EPI_MULDGELU) X(TNR_EPI_MULDGELU | TNR_EPI_COLSUM)              \
     X(TNR_EPI_BIAS | TNR_EPI_TANH | TNR_EPI_OUTF32) X(TNR_EPI_BIAS | TNR_EPI_RES | TNR_EPI_DROPOUT)
-// Counter sets of the ping-pong kernel's tile queue (the ONE piece of device state the library keeps, include/tnr_hip.h):
-// 128 sets in a __device__ array, one per (device, stream) the kernel has been launched on -- launches of a stream run in order,
-// so each finds the set its predecessor returned to zero, and launches of different streams never share one.  A set is zeroed
-// by a hipMemsetAsync on its stream when the stream is first bound and again by tnr_gemm_queue_reset(); every launch leaves
-// it at zero (the last workgroup out resets it).  The table never drains a device and never changes the current device: when
-// it is full the launch is refused (TNR_EUNSUPPORTED) and the caller either reuses fewer streams or runs with option "pp" = 0.
-// ONE table for both builds of this file (bf16 and -DTNR_BUILD_F16): it is defined in the bf16 translation unit and the fp16
-// one calls into it (tnr_pp_queue_of, declared in common.h), so a stream that launches kernels of both builds is bound once and
-// tnr_gemm_queue_reset reaches the counters whichever build's kernel was aborted.
+// (the tile queue's counter sets, the routing and the tilings are host state and host arithmetic shared by both builds of this file:
+// gemm_plan.hip, declared in common.h)
 constexpr int PP_LDS = LDS3_BYTES + 64;
-[[maybe_unused]] constexpr int PP_QUEUE_SETS = 128;
-#ifdef TNR_BUILD_F16
-static unsigned* pp_queue_of(hipStream_t st, bool reset = false) { return tnr_pp_queue_of(st, reset); }
-#else
-__device__ unsigned g_pp_queue[PP_QUEUE_SETS * PP_Q_SET];
-static unsigned* pp_queue_of(hipStream_t st, bool reset = false) { return tnr_pp_queue_of(st, reset); }
-unsigned* tnr_pp_queue_of(void* stream, bool reset) {
-    hipStream_t st = (hipStream_t)stream;
-    struct Slot { int dev; hipStream_t st; };
-    static std::mutex mu;
-    static Slot slots[PP_QUEUE_SETS];
-    static int nslot = 0;
-    static unsigned* base[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { tnr_set_error("tnr_gemm_nt: no current device"); return nullptr; }
-    std::lock_guard<std::mutex> lk(mu);
-    if (!base[dev] && hipGetSymbolAddress((void**)&base[dev], HIP_SYMBOL(g_pp_queue)) != hipSuccess) {
-        tnr_set_error("tnr_gemm_nt: tile-queue symbol not found");
-        return nullptr;
-    }
-    unsigned* set = nullptr;
-    for (int i = 0; i < nslot && !set; ++i)
-        if (slots[i].dev == dev && slots[i].st == st) set = base[dev] + i * PP_Q_SET;
-    const bool fresh = !set;
-    if (!set) {
-        if (nslot == PP_QUEUE_SETS) {
-            tnr_set_error("tnr_gemm_nt: more than %d (device, stream) pairs have launched the persistent GEMM in this process "
-                          "(reuse streams, or tnr_gemm_set_option(\"pp\", 0) for the kernels without a tile queue)", PP_QUEUE_SETS);
-            return nullptr;
-        }
-        slots[nslot] = Slot{dev, st};
-        set = base[dev] + (nslot++) * PP_Q_SET;
-    }
-    if ((fresh || reset) && hipMemsetAsync(set, 0, PP_Q_SET * sizeof(unsigned), st) != hipSuccess) {
-        tnr_set_error("tnr_gemm_nt: could not zero the tile-queue counters");
-        return nullptr;
-    }
-    return set;
-}
-#endif
-
-#ifndef TNR_BUILD_F16
-// Zero the calling stream's tile-queue counters (stream-ordered).  Only needed after a launch on that stream was aborted (device
-// fault, process-level recovery): a completed launch always leaves them at zero.
-extern "C" int tnr_gemm_queue_reset(void* stream) {
-    return pp_queue_of((hipStream_t)stream, true) ? TNR_OK : TNR_EUNSUPPORTED;
-}
-#endif
 
 template <int MI>
 static void pp_launch(const NTArgs& g, unsigned grid, hipStream_t st) {
@@ -1596,16 +1394,6 @@ static void pp_launch(const NTArgs& g, unsigned grid, hipStream_t st) {
     default: hipLaunchKernelGGL((gemm_nt_pp_kernel<MI, -1>), dim3(grid), dim3(512), PP_LDS, st, g); break;
     }
 }
-
-#ifndef TNR_BUILD_F16
-// host-only (no HIP call): the tiling the persistent kernel would use on a device with n_cu compute units
-extern "C" int tnr_gemm_nt_plan(int64_t M, int64_t N, int flags, int n_cu, int* mi, int* panels, int* tall) {
-    TNR_CHECK_ARG(M >= 1 && N >= 256 && (N % 256) == 0 && n_cu >= 1 && mi && panels && tall, "tnr_gemm_nt_plan: bad argument");
-    const PpPlan pl = pp_plan(M, N, flags, n_cu);
-    *mi = pl.mi; *panels = pl.P; *tall = pl.x;
-    return TNR_OK;
-}
-#endif
 
 extern "C" int TNR_NAME(tnr_gemm_nt_route)(int64_t M, int64_t N, int64_t K, int flags) {
     return nt_route(M, N, K, flags, device_cus());
@@ -1680,7 +1468,7 @@ extern "C" int TNR_NAME(tnr_gemm_nt_do_split)(const void* A, int64_t lda, const 
     default: {                                          // the persistent kernel, 224- or 256-row instance
         const PpPlan pl = pp_plan(M, N, flags, n_cu);
         g.mix_p = pl.P; g.mix_x = pl.x;
-        if (!(g.queue = pp_queue_of(st))) return TNR_EUNSUPPORTED;
+        if (!(g.queue = tnr_pp_queue_of(st, false))) return TNR_EUNSUPPORTED;
         const unsigned grid = (unsigned)std::min<int64_t>((int64_t)pl.P * (N / 256), std::max(n_cu, 8));   // >= 8: every XCD label needs a workgroup
         if (pl.mi == 7) pp_launch<7>(g, grid, st);
         else pp_launch<8>(g, grid, st);
@@ -1736,15 +1524,14 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_ex)(const void* dY, int64_t lddy, cons
         TNGroup grp{};
         grp.p[0] = g;
         for (int i = 1; i <= TN_MAXP; ++i) grp.ubase[i] = units;
-        tn_group_ranges(grp, 1);
-        if (!(grp.queue = pp_queue_of((hipStream_t)stream))) return TNR_EUNSUPPORTED;
+        tn_group_ranges(grp.ubase, &g.tiles_per_split, 1, grp.xb);
+        if (!(grp.queue = tnr_pp_queue_of(stream, false))) return TNR_EUNSUPPORTED;
         dim3 pgrid((unsigned)std::min<int64_t>(units, std::max(device_cus(), 8)));
         hipLaunchKernelGGL(gemm_tn_rs_kernel, pgrid, dim3(512), RS_LDS, (hipStream_t)stream, grp);
     }
     TNR_CHECK_LAUNCH("tnr_gemm_tn_wgrad");
     int64_t NK = N * K;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((NK / 4 + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const float*)ws, splits, NK, (int)K, dW, lddw, accumulate, out_scale);
+    slab_reduce_launch(SlabSum{ws, dW, NK, lddw, splits, (int)K, accumulate, out_scale}, (hipStream_t)stream);
     TNR_CHECK_LAUNCH("tnr_gemm_tn_wgrad/reduce");
     return TNR_OK;
 }
@@ -1774,8 +1561,9 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_group)(const tnr_wgrad_problem_t* p, i
     for (int i = 0; i < n; ++i) pp = pp && p[i].N >= 256 && p[i].K >= 256 && (p[i].N % 256) == 0 && (p[i].K % 256) == 0;
     if (!pp) return one_by_one();              // a shape off the persistent kernel's route (or one problem)
     TNGroup grp{};
-    SlabGroup sg{};
-    int64_t units = 0, maxblk = 0;
+    SlabSum sg[TN_MAXP] = {};
+    int tps_of[TN_MAXP];
+    int64_t units = 0;
     for (int i = 0; i < n; ++i) {
         const tnr_wgrad_problem_t& q = p[i];
         const bool chained = q.accumulate == 2;
@@ -1794,17 +1582,17 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_group)(const tnr_wgrad_problem_t* p, i
                       "tnr_gemm_tn_wgrad_group: problem %d: %d rows per split x leading dimension %ld exceed the 2 GiB a unit may span - raise "
                       "`splits`", i, tps * 64, (long)std::max(q.lddy, q.ldx));
         const int h = head_of(i);
-        float* const ws_i = chained ? (float*)sg.ws[h] + (int64_t)sg.splits[h] * q.N * q.K : q.ws;   // behind the chain's slabs so far
+        float* const ws_i = chained ? (float*)sg[h].ws + (int64_t)sg[h].splits * q.N * q.K : q.ws;   // behind the chain's slabs so far
         grp.p[i] = TNArgs{(const bf16*)q.dY, q.lddy, (const bf16*)q.X, q.ldx, ws_i, Mt, (int)q.N, (int)q.K, tps, splits, nullptr};
+        tps_of[i] = tps;
         grp.ubase[i] = (int)units;
         units += (q.N / 256) * (q.K / 256) * splits;
-        sg.ws[i] = ws_i; sg.out[i] = q.dW; sg.ldo[i] = q.lddw; sg.K[i] = (int)q.K; sg.out_scale[i] = q.out_scale;
         if (chained) {                      // its slabs are summed with the head's: no slab sum of its own
-            sg.splits[h] += splits; sg.NK[i] = 0; sg.splits[i] = 0; sg.accumulate[i] = 0;
+            sg[i] = SlabSum{ws_i, q.dW, 0, q.lddw, 0, (int)q.K, 0, q.out_scale};
+            sg[h].splits += splits;
         } else {
-            sg.NK[i] = q.N * q.K; sg.splits[i] = splits; sg.accumulate[i] = q.accumulate;
+            sg[i] = SlabSum{ws_i, q.dW, q.N * q.K, q.lddw, splits, (int)q.K, q.accumulate, q.out_scale};
         }
-        maxblk = std::max<int64_t>(maxblk, (q.N * q.K / 4 + 255) / 256);
     }
     if (units < 8) {
         // fewer units than XCD labels: the grid min(units, ...) would leave labels that tn_group_ranges gives work without a
@@ -1812,16 +1600,16 @@ extern "C" int TNR_NAME(tnr_gemm_tn_wgrad_group)(const tnr_wgrad_problem_t* p, i
         return one_by_one();
     }
     for (int i = n; i <= TN_MAXP; ++i) grp.ubase[i] = (int)units;
-    tn_group_ranges(grp, n);
+    tn_group_ranges(grp.ubase, tps_of, n, grp.xb);
     TNR_ONCE_PER_DEVICE({
         (void)hipFuncSetAttribute((const void*)gemm_tn_rs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS);
     });
-    if (!(grp.queue = pp_queue_of((hipStream_t)stream))) return TNR_EUNSUPPORTED;
+    if (!(grp.queue = tnr_pp_queue_of(stream, false))) return TNR_EUNSUPPORTED;
     const int n_cu = device_cus();
     const dim3 ggrid((unsigned)std::min<int64_t>(units, std::max(n_cu, 8)));
     hipLaunchKernelGGL(gemm_tn_rs_kernel, ggrid, dim3(512), RS_LDS, (hipStream_t)stream, grp);
     TNR_CHECK_LAUNCH("tnr_gemm_tn_wgrad_group");
-    hipLaunchKernelGGL(slab_reduce_group_kernel, dim3((unsigned)maxblk, (unsigned)n), dim3(256), 0, (hipStream_t)stream, sg);
+    slab_reduce_group_launch(sg, n, (hipStream_t)stream);
     TNR_CHECK_LAUNCH("tnr_gemm_tn_wgrad_group/reduce");
     return TNR_OK;
 }

@@ -1,5 +1,5 @@
-// Fused AMSGrad over the flat trainable-parameter buffer + refresh of the bf16 weight copies
-// (row-major and transposed) the GEMMs read.  torch.optim.Adam(amsgrad=True) semantics (run.py:134).
+// Fused AMSGrad over the flat trainable-parameter buffer + the non-finite-gradient guard of dynamic loss scaling, all fp32.
+// torch.optim.Adam(amsgrad=True) semantics (run.py:134).  (The refresh of the 16-bit weight copies: norm_embed.hip.)
 #include <algorithm>
 
 #include "common.h"
@@ -88,47 +88,8 @@ __global__ void grad_nonfinite_count_kernel(unsigned* guard, unsigned stamp) {  
     if (guard[0] == stamp) guard[1] += 1;
 }
 
-// one workgroup per 32x32 tile of some weight matrix (descriptor table on device)
-__global__ __launch_bounds__(256) void refresh_kernel(const int64_t* __restrict__ desc, int n_desc,
-                                                      const int64_t* __restrict__ tile_start) {
-    __shared__ float t[32][33];
-    int64_t tile = blockIdx.x;
-    int di = 0;
-    while (di + 1 < n_desc && tile >= tile_start[di + 1]) ++di;
-    const int64_t* d = desc + (int64_t)di * 8;
-    const float* src = (const float*)d[0];
-    const int64_t rows = d[1], cols = d[2];
-    bf16* dst = (bf16*)d[3];
-    const int64_t ld = d[4];
-    bf16* dstT = (bf16*)d[5];
-    const int64_t ldT = d[6];
-    const int64_t local = tile - tile_start[di];
-    const int64_t tcols = (cols + 31) / 32;
-    const int64_t r0 = (local / tcols) * 32, c0 = (local % tcols) * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;    // 32 x 8
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int64_t r = r0 + ty + 8 * k, c = c0 + tx;
-        float v = (r < rows && c < cols) ? src[r * cols + c] : 0.f;
-        t[ty + 8 * k][tx] = v;
-        if (dst && r < rows && c < cols) dst[r * ld + c] = (bf16)v;
-    }
-    __syncthreads();
-    if (dstT) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            int64_t c = c0 + ty + 8 * k, r = r0 + tx;
-            if (r < rows && c < cols) dstT[c * ldT + r] = (bf16)t[tx][ty + 8 * k];
-        }
-    }
-}
-
 }  // namespace
 
-#ifndef TNR_BUILD_F16
-extern "C" int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
-                                        float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
-                                        unsigned stamp, unsigned known_skips, void* stream);
 extern "C" int tnr_amsgrad_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
                                 float beta1, float beta2, float eps, float grad_scale, void* stream) {
     return tnr_amsgrad_step_guarded(p, g, m, v, vmax, n, step, lr, beta1, beta2, eps, grad_scale, nullptr, 0u, 0u, stream);
@@ -180,16 +141,5 @@ extern "C" int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, floa
         hipLaunchKernelGGL(amsgrad_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m,
                            v, vmax, n, f, beta1, beta2, eps, grad_scale, guard, stamp);
     TNR_CHECK_LAUNCH("tnr_amsgrad_step");
-    return TNR_OK;
-}
-
-#endif
-
-extern "C" int TNR_NAME(tnr_refresh_shadows)(const int64_t* desc, int n_desc, int64_t total_tiles, const int64_t* tile_start,
-                                   void* stream) {
-    TNR_CHECK_ARG(desc && tile_start && n_desc >= 1 && total_tiles >= 1, "tnr_refresh_shadows: bad argument");
-    hipLaunchKernelGGL(refresh_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, desc, n_desc,
-                       tile_start);
-    TNR_CHECK_LAUNCH("tnr_refresh_shadows");
     return TNR_OK;
 }
