@@ -630,10 +630,6 @@ def test_reduce_rows_shapes():
 
 
 # ------------------------------------------------------------------------------------------------ fp16 build
-def hf(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.float16).float().numpy()
-
-
 def test_f16_variants_gemm_attention_ln():
     """Same sources compiled with IEEE half: exact integer GEMMs (NT + wgrad) and attention / LayerNorm spot checks."""
     rs = np.random.RandomState(5)

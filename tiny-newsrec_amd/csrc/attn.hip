@@ -296,7 +296,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16* __restrict
             for (int e = 0; e < 4; ++e) {
                 float p = __expf(sn[4 * g + e] * 0.125f + mk + relcol[4 * g + e] - lse[e]);
                 sn[4 * g + e] = p * dm[e];                                // what multiplied V in the forward pass
-                dpn[4 * g + e] = p * (dpn[4 * g + e] * dm[e] - dd[e]);    // dS
+                // dP m rounded on its own, as the transposed pass rounded it before it summed delta: contracted into the
+                // subtraction the product stays exact, and what delta's rounded copy leaves of it (half an ulp of dP m) would
+                // pass for dS - all of dS where it cancels (one key: dS = 0, dk came out as 2.6e-8)
+                float dpm;
+                {
+#pragma clang fp contract(off)
+                    dpm = dpn[4 * g + e] * dm[e];
+                }
+                dpn[4 * g + e] = p * (dpm - dd[e]);                       // dS
             }
         }
     }
