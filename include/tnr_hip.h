@@ -87,6 +87,26 @@ int tnr_embed_ln_fwd_indexed(const int32_t* news_combined, const int32_t* nidx, 
                              const float* word, const float* pos, const float* type0, const float* gamma,
                              const float* beta, float eps, void* out, float* mask_add, void* stream);
 
+/* Backward of the two forms above (BertEmbeddings.forward, tnlrv3/modeling.py:153-178; word table with padding_idx = 0, :138),
+ * same token addressing; pos_ids (nullable) and drop (nullable, the DROP_EMB site) as in tnr_embed_ln_fwd_do.  The forward saves
+ * nothing: x = word[id] + pos[pi] + type0 and its row statistics are recomputed in fp32 exactly as the forward computes them, the
+ * dropout mask is regenerated.  dy (N*L, H) 16-bit = gradient w.r.t. the embedding output at the caller's loss scale.  With
+ * g = dy * mask * gamma:
+ *   dx (N*L, H) FP32 = inv_scale * rstd * (g - mean(g) - xh * mean(g * xh))      the true gradient of every token's summed row:
+ *        the word / position / type tables' gradients are sums of its rows (tnr_scatter_sum_rows, tnr_colsum)
+ *   part (nblk, 2H) fp32 = per-block [dgamma | dbeta] partial sums AT dy's SCALE (inv_scale is not applied: the reduction
+ *        carries it, tnr_reduce_multi's descriptor scale), for tnr_reduce_rows / tnr_reduce_multi; fixed order.
+ * H = 256 V, V = 1..4.  Token ids must be rows of `word`, position ids rows of `pos` (as in the forward). */
+int tnr_embed_ln_bwd(const int64_t* tok, int64_t n_seq, int L, int H, const void* dy, const float* word, const float* pos,
+                     const float* type0, const float* gamma, float eps, float inv_scale, float* dx, float* part,
+                     const tnr_dropout_t* drop, const int32_t* pos_ids, void* stream);
+int tnr_embed_ln_bwd_indexed(const int32_t* news_combined, const int32_t* nidx, int64_t n_seq, int L, int H, const void* dy,
+                             const float* word, const float* pos, const float* type0, const float* gamma, float eps,
+                             float inv_scale, float* dx, float* part, const tnr_dropout_t* drop, const int32_t* pos_ids,
+                             void* stream);
+int64_t tnr_embed_ln_bwd_part_elems(int64_t n_tok, int H);   /* workspace good for every token count <= n_tok */
+int64_t tnr_embed_ln_bwd_blocks(int64_t n_tok);              /* partial rows (nblk) written for exactly n_tok tokens */
+
 /* C[M,N] = epilogue(A[M,K] . B[N,K]^T).  bf16 operands, fp32 MFMA accumulation.
  * Forward Linear (tnlrv3/modeling.py:236-248, transformers BertSelfOutput/BertIntermediate/BertOutput),
  * and its dgrad when B is the transposed weight copy.  N % 128 == 0, K % 64 == 0, any M >= 1.
@@ -290,6 +310,15 @@ int tnr_gather_rows(const float* tbl, int64_t R, const int32_t* idx, int64_t n_i
 int tnr_segment_sum_rows(const float* src, const int32_t* order, const int32_t* seg, int64_t n_seg, int D,
                          float* out, void* stream);
 
+/* Deterministic row scatter-sum (the backward of an embedding lookup, tnlrv3/modeling.py:138, 153-178): for every run of equal
+ * keys in keys_sorted (n, ascending),   table[key, :] (+)= sum over the run of src[order[j], :]   in increasing j with a fixed
+ * reduction tree (tnr_segment_sum_rows' scheme); the runs are found on the device.  order (n) = row of src per sorted position
+ * (the permutation a stable sort of the keys returns), every entry in [0, rows of src).  Keys equal to skip_key (padding_idx: that
+ * row never gets a gradient) and keys outside [0, table_rows) are skipped; rows no key names are NOT touched (the caller zeroes
+ * the table region).  No floating-point atomics: bit-identical from run to run.  D % 4 == 0, D <= 2048. */
+int tnr_scatter_sum_rows(const float* src, int64_t n, int D, const int32_t* keys_sorted, const int32_t* order, int32_t skip_key,
+                         float* table, int64_t table_rows, int accumulate, void* stream);
+
 /* UserEncoder.forward (model_bert.py:155-176, model != NRMS) + scorer bmm (:204 / :286-287) for
  * `n_model` encoders at once (student and/or frozen teachers), one workgroup per (impression, model).
  * vec: (n_model, R, D) fp32 row tables ; hidx (B,U) / cidx (B,C) int32 row ids ; mask (B,U) fp32.
@@ -462,6 +491,13 @@ int tnr_embed_ln_fwd_f16(const int64_t* tok, int64_t n_seq, int L, int H, const 
 int tnr_embed_ln_fwd_indexed_f16(const int32_t* news_combined, const int32_t* nidx, int64_t n_seq, int L, int H,
                              const float* word, const float* pos, const float* type0, const float* gamma,
                              const float* beta, float eps, void* out, float* mask_add, void* stream);
+int tnr_embed_ln_bwd_f16(const int64_t* tok, int64_t n_seq, int L, int H, const void* dy, const float* word, const float* pos,
+                     const float* type0, const float* gamma, float eps, float inv_scale, float* dx, float* part,
+                     const tnr_dropout_t* drop, const int32_t* pos_ids, void* stream);
+int tnr_embed_ln_bwd_indexed_f16(const int32_t* news_combined, const int32_t* nidx, int64_t n_seq, int L, int H, const void* dy,
+                             const float* word, const float* pos, const float* type0, const float* gamma, float eps,
+                             float inv_scale, float* dx, float* part, const tnr_dropout_t* drop, const int32_t* pos_ids,
+                             void* stream);
 int tnr_gemm_nt_f16(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                 int64_t M, int64_t N, int64_t K, const float* bias, const void* res, int64_t ldres,
                 void* aux, int64_t ldaux, int flags, void* stream);

@@ -179,6 +179,11 @@ constexpr int LNB_ROWS = 128;  // rows per block (8 half waves x 16 rows); short
 static inline int lnb_rows(int64_t M) { return M >= 32768 ? LNB_ROWS : 32; }
 static inline int64_t lnb_blocks(int64_t M) { return (M + lnb_rows(M) - 1) / lnb_rows(M); }
 
+// embedding-LayerNorm backward (norm_embed.hip; workspace sizes: util_f32.hip): tokens per block (four waves, a token per wave
+// and turn); short inputs use 16 so that every CU gets work
+static inline int embwd_rows(int64_t n_tok) { return n_tok >= 32768 ? 64 : 16; }
+static inline int64_t embwd_blocks(int64_t n_tok) { return (n_tok + embwd_rows(n_tok) - 1) / embwd_rows(n_tok); }
+
 // column sums: block = 256 columns (64 threads x 4) x 4 row lanes over `rows_per_block` rows: 512 for tall inputs, 64 for short
 // ones (a 1792-row input on 512-row blocks was 4 workgroups walking 128 dependent loads each: 33 us for 1.8 MB)
 constexpr int CS_ROWS = 512;

@@ -260,6 +260,60 @@ __global__ __launch_bounds__(1024) void segment_sum_rows_kernel(const float* __r
     }
 }
 
+// table[key, :] (+)= sum over a run of equal keys in keys_sorted of src[order[j], :]: the gradient rows of an embedding table
+// (nn.Embedding's backward, tnlrv3/modeling.py:138, 153-178) without floating-point atomics.  One workgroup per SORTED POSITION; only
+// the first position of a run works (its end is found by bisection: the keys are sorted), every other one leaves at once.  Runs of
+// skip_key (padding_idx: that row never gets a gradient) and of keys outside the table are skipped, rows no key names are not
+// touched.  The sum is segment_sum_rows_kernel's: wave w takes entries w, w + 16, ... with four accumulators, the 16 partial rows
+// are added in wave order - the same bits every run.
+__global__ __launch_bounds__(1024) void scatter_sum_rows_kernel(const float* __restrict__ src, int64_t n, int D,
+                                                                const int32_t* __restrict__ keys, const int32_t* __restrict__ order,
+                                                                int32_t skip_key, float* __restrict__ table, int64_t table_rows,
+                                                                int accumulate) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];      // [16][D]
+    const int64_t j0 = blockIdx.x;
+    const int32_t key = keys[j0];
+    if (j0 > 0 && keys[j0 - 1] == key) return;                      // not the first of its run
+    if (key == skip_key || key < 0 || (int64_t)key >= table_rows) return;
+    int64_t lo = j0 + 1, hi = n;                                    // first position in (j0, n] whose key differs
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] == key) lo = mid + 1; else hi = mid;
+    }
+    const int64_t j1 = lo;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float* out = table + (int64_t)key * D;
+    if (j1 - j0 <= 4) {
+        if (w == 0)
+            for (int c = lane * 4; c < D; c += 256) {
+                f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
+                for (int64_t j = j0; j < j1; ++j) a += *(const f32x4*)(src + (int64_t)order[j] * D + c);
+                if (accumulate) a += *(const f32x4*)(out + c);
+                *(f32x4*)(out + c) = a;
+            }
+        return;
+    }
+    for (int c = lane * 4; c < D; c += 256) {
+        f32x4 a[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        int64_t j = j0 + w;
+        for (; j + 48 < j1; j += 64) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[q] += *(const f32x4*)(src + (int64_t)order[j + 16 * q] * D + c);
+        }
+        for (int q = 0; j < j1; j += 16, ++q) a[q & 3] += *(const f32x4*)(src + (int64_t)order[j] * D + c);
+        *(f32x4*)(sm + w * D + c) = (a[0] + a[1]) + (a[2] + a[3]);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < D; c += 1024) {
+        float t = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) t += sm[q * D + c];
+        out[c] = accumulate ? out[c] + t : t;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // UserEncoder (model_bert.py:155-176) + scorer (:204).  One workgroup per (impression, model).
 constexpr int MAXU = 64;
@@ -1037,6 +1091,16 @@ extern "C" int tnr_segment_sum_rows(const float* src, const int32_t* order, cons
     hipLaunchKernelGGL(segment_sum_rows_kernel, dim3((unsigned)n_seg), dim3(1024), 16 * D * sizeof(float),
                        (hipStream_t)stream, src, order, seg, D, out);
     TNR_CHECK_LAUNCH("tnr_segment_sum_rows");
+    return TNR_OK;
+}
+
+extern "C" int tnr_scatter_sum_rows(const float* src, int64_t n, int D, const int32_t* keys_sorted, const int32_t* order,
+                                    int32_t skip_key, float* table, int64_t table_rows, int accumulate, void* stream) {
+    TNR_CHECK_ARG(src && keys_sorted && order && table && n >= 1 && n <= 0x7FFFFFFF && table_rows >= 1 && D >= 4 && (D % 4) == 0 &&
+                  D <= 2048, "tnr_scatter_sum_rows: bad argument");
+    hipLaunchKernelGGL(scatter_sum_rows_kernel, dim3((unsigned)n), dim3(1024), 16 * D * sizeof(float), (hipStream_t)stream, src, n,
+                       D, keys_sorted, order, skip_key, table, table_rows, accumulate);
+    TNR_CHECK_LAUNCH("tnr_scatter_sum_rows");
     return TNR_OK;
 }
 

@@ -81,6 +81,94 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const TokT* __restrict__ 
     }
 }
 
+// Backward of embed_ln_kernel (tnlrv3/modeling.py:153-178).  The forward saves nothing: x = word[id] + pos[pi] + type0 and the
+// row statistics are recomputed exactly as it computes them (one wave per token, row_stats), the DROP_EMB mask of :177 is
+// regenerated at element t * H + c.  With g = dy * mask * gamma:
+//   dx = inv_scale * rstd * (g - mean(g) - xh * mean(g * xh))   fp32 rows: what the scatter / column sums of the tables add up
+//   part[block] = [sum dy * mask * xh | sum dy * mask]           one row per block, at dy's (loss) scale, summed in a fixed order
+// A block takes rows_per_block consecutive tokens (embwd_rows, common.h), four at a time.
+template <int V, typename TokT>
+__global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const TokT* __restrict__ tok, const int32_t* __restrict__ nidx,
+                                                           int64_t n_tok, int L, const bf16* __restrict__ dy,
+                                                           const float* __restrict__ word, const float* __restrict__ pos,
+                                                           const float* __restrict__ type0, const float* __restrict__ gamma,
+                                                           float eps, float inv_scale, float* __restrict__ dx,
+                                                           float* __restrict__ part, int rows_per_block, TnrDrop drop,
+                                                           const int32_t* __restrict__ pos_ids) {
+    const int H = 256 * V;
+    __shared__ float red[4][2][256 * V];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float gm[V][4], dg[V][4], db[V][4];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const f32x4 t0 = *(const f32x4*)(gamma + v * 256 + lane * 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { gm[v][r] = t0[r]; dg[v][r] = 0.f; db[v][r] = 0.f; }
+    }
+    for (int it = 0; it < rows_per_block / 4; ++it) {
+        const int64_t t = (int64_t)blockIdx.x * rows_per_block + it * 4 + w;
+        if (t >= n_tok) break;
+        const int64_t n = t / L;
+        const int i = (int)(t - n * L);
+        const int64_t trow = nidx ? (int64_t)nidx[n] : n;
+        const int64_t id = (int64_t)tok[trow * 2 * L + i];
+        const int pi = pos_ids ? pos_ids[trow * L + i] : i;
+        float x[V][4], g[V][4];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int c = v * 256 + lane * 4;
+            const f32x4 a = *(const f32x4*)(word + id * H + c);
+            const f32x4 b = *(const f32x4*)(pos + (int64_t)pi * H + c);
+            const f32x4 d = *(const f32x4*)(type0 + c);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[v][r] = a[r] + b[r] + d[r];
+        }
+        float mean, rstd;
+        row_stats<V>(x, H, mean, rstd, eps);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int c = v * 256 + lane * 4;
+            const bf16x4 d = *(const bf16x4*)(dy + t * H + c);
+            float dm[4] = {1.f, 1.f, 1.f, 1.f};
+            if (drop.thresh) tnr_drop4(drop, (uint64_t)t * H + c, dm);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float dyv = (float)d[r] * dm[r];
+                x[v][r] = (x[v][r] - mean) * rstd;           // xh
+                g[v][r] = dyv * gm[v][r];
+                s1 += g[v][r];
+                s2 += g[v][r] * x[v][r];
+                dg[v][r] += dyv * x[v][r];
+                db[v][r] += dyv;
+            }
+        }
+        s1 = wave_sum(s1) / (float)H;
+        s2 = wave_sum(s2) / (float)H;
+        const float k = inv_scale * rstd;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            f32x4 o;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] = k * (g[v][r] - s1 - x[v][r] * s2);
+            *(f32x4*)(dx + t * H + v * 256 + lane * 4) = o;
+        }
+    }
+    // the four waves own the same columns: combined through LDS in wave order
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            red[w][0][v * 256 + lane * 4 + r] = dg[v][r];
+            red[w][1][v * 256 + lane * 4 + r] = db[v][r];
+        }
+    __syncthreads();
+    for (int c = threadIdx.x; c < 2 * H; c += 256) {
+        const int k = c / H, h = c - k * H;
+        part[(int64_t)blockIdx.x * 2 * H + c] = (red[0][k][h] + red[1][k][h]) + (red[2][k][h] + red[3][k][h]);
+    }
+}
+
 __device__ __forceinline__ float half_sum(float v) {      // over the 32 lanes of this lane's half wave
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -352,6 +440,45 @@ extern "C" int TNR_NAME(tnr_embed_ln_fwd_indexed)(const int32_t* news_combined, 
                                         const float* beta, float eps, void* out, float* mask_add, void* stream) {
     return TNR_NAME(tnr_embed_ln_fwd_indexed_do)(news_combined, nidx, n_seq, L, H, word, pos, type0, gamma, beta, eps, out, mask_add,
                                                  nullptr, nullptr, stream);
+}
+
+extern "C" int TNR_NAME(tnr_embed_ln_bwd)(const int64_t* tok, int64_t n_seq, int L, int H, const void* dy, const float* word,
+                                const float* pos, const float* type0, const float* gamma, float eps, float inv_scale, float* dx,
+                                float* part, const tnr_dropout_t* drop, const int32_t* pos_ids, void* stream) {
+    TnrDrop dd;
+    if (int rc = tnr_make_drop(drop, &dd, "tnr_embed_ln_bwd")) return rc;
+    TNR_CHECK_ARG(tok && dy && word && pos && type0 && gamma && dx && part, "tnr_embed_ln_bwd: null pointer");
+    TNR_CHECK_ARG(L >= 1 && L <= 512 && n_seq >= 1, "tnr_embed_ln_bwd: need 1<=L<=512");
+    TNR_CHECK_ARG(H == 768 || H == 256 || H == 512 || H == 1024, "tnr_embed_ln_bwd: H must be 256/512/768/1024");
+    const int64_t n_tok = n_seq * L;
+    const int rows = embwd_rows(n_tok);
+    dim3 grid((unsigned)embwd_blocks(n_tok)), blk(256);
+    hipStream_t st = (hipStream_t)stream;
+#define LAUNCH(V) hipLaunchKernelGGL((embed_ln_bwd_kernel<V, int64_t>), grid, blk, 0, st, tok, (const int32_t*)nullptr, n_tok, L, (const bf16*)dy, word, pos, type0, gamma, eps, inv_scale, dx, part, rows, dd, pos_ids)
+    switch (H / 256) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); }
+#undef LAUNCH
+    TNR_CHECK_LAUNCH("tnr_embed_ln_bwd");
+    return TNR_OK;
+}
+
+extern "C" int TNR_NAME(tnr_embed_ln_bwd_indexed)(const int32_t* news_combined, const int32_t* nidx, int64_t n_seq, int L, int H,
+                                        const void* dy, const float* word, const float* pos, const float* type0,
+                                        const float* gamma, float eps, float inv_scale, float* dx, float* part,
+                                        const tnr_dropout_t* drop, const int32_t* pos_ids, void* stream) {
+    TnrDrop dd;
+    if (int rc = tnr_make_drop(drop, &dd, "tnr_embed_ln_bwd_indexed")) return rc;
+    TNR_CHECK_ARG(news_combined && nidx && dy && word && pos && type0 && gamma && dx && part, "tnr_embed_ln_bwd_indexed: null pointer");
+    TNR_CHECK_ARG(L >= 1 && L <= 512 && n_seq >= 1, "tnr_embed_ln_bwd_indexed: need 1<=L<=512");
+    TNR_CHECK_ARG(H == 768 || H == 256 || H == 512 || H == 1024, "tnr_embed_ln_bwd_indexed: H must be 256/512/768/1024");
+    const int64_t n_tok = n_seq * L;
+    const int rows = embwd_rows(n_tok);
+    dim3 grid((unsigned)embwd_blocks(n_tok)), blk(256);
+    hipStream_t st = (hipStream_t)stream;
+#define LAUNCH(V) hipLaunchKernelGGL((embed_ln_bwd_kernel<V, int32_t>), grid, blk, 0, st, news_combined, nidx, n_tok, L, (const bf16*)dy, word, pos, type0, gamma, eps, inv_scale, dx, part, rows, dd, pos_ids)
+    switch (H / 256) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); }
+#undef LAUNCH
+    TNR_CHECK_LAUNCH("tnr_embed_ln_bwd_indexed");
+    return TNR_OK;
 }
 
 extern "C" int TNR_NAME(tnr_pool_fwd)(const void* y, float* nv, int64_t n_seq, int L, int H, int mean, void* stream) {

@@ -126,6 +126,12 @@ extern "C" int64_t tnr_ln_bwd_part_elems(int64_t M, int H) {
     return (nb > nb_short ? nb : nb_short) * 3 * H;
 }
 extern "C" int64_t tnr_ln_bwd_blocks(int64_t M) { return lnb_blocks(M); }
+// the same for tnr_embed_ln_bwd: one [dgamma | dbeta] row of 2 H floats per block
+extern "C" int64_t tnr_embed_ln_bwd_part_elems(int64_t n_tok, int H) {
+    int64_t nb = embwd_blocks(n_tok), nb_short = embwd_blocks(n_tok < 32767 ? n_tok : 32767);
+    return (nb > nb_short ? nb : nb_short) * 2 * H;
+}
+extern "C" int64_t tnr_embed_ln_bwd_blocks(int64_t n_tok) { return embwd_blocks(n_tok); }
 
 extern "C" int tnr_reduce_rows(const float* part, int64_t rows, int64_t stride, int64_t n, float* out, int accumulate,
                                void* stream) {

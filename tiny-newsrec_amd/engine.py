@@ -51,7 +51,7 @@ class EngineConfig:
     def __init__(self, n_layers=4, trainable_layers=(2, 3), hidden=768, heads=12, inter=3072, news_dim=256,
                  news_query=200, user_query=200, num_teachers=4, user_log_length=50, npratio=4, num_words=30,
                  user_log_mask=False, temperature=1.0, coef=0.2, vocab=30522, max_pos=512, type_vocab=2,
-                 ln_eps=1e-12, stage1=False, pooling="att", nrms_heads=0, pos_pad_id=None):
+                 ln_eps=1e-12, stage1=False, pooling="att", nrms_heads=0, pos_pad_id=None, train_embeddings=False):
         """stage1=True: the DistillModel of Post-train_KD.ipynb (no user encoders: parameters are
         student.news_encoder.* and transform_matrix.* only; user_log_length is 0, npratio+1 titles per body)."""
         self.stage1 = stage1
@@ -59,6 +59,17 @@ class EngineConfig:
         # 'roberta' additionally takes its position rows from the token ids -- cumulative count of non-pad tokens + padding_idx
         # (transformers create_position_ids_from_input_ids) -- with type_vocab 1, max_pos 514 and ln_eps 1e-5 from its config
         self.pos_pad_id = pos_pad_id
+        # train_embeddings: bert.embeddings.* (word / position / token-type tables, embedding LayerNorm) join the trainable set.  The
+        # reference freezes them with the rest of bert_model (run.py:101-112; its --freeze_embedding flag is read by nothing), so
+        # this is an opt-in extension: off, every path and buffer is what it was.  On, the backward runs down through every layer
+        # (layers outside trainable_layers pass the gradient on without weight gradients) into tnr_embed_ln_bwd.
+        self.train_embeddings = bool(train_embeddings)
+        assert not (self.train_embeddings and stage1), \
+            "train_embeddings with stage1: the post-training notebooks freeze the embeddings and the joint title/body passes have no embedding backward"
+        assert not (self.train_embeddings and pos_pad_id is not None), \
+            "train_embeddings with pos_pad_id (roberta): its padding position rows are not covered by the engine's embedding backward"
+        assert not self.train_embeddings or len(tuple(trainable_layers)) > 0, \
+            "train_embeddings needs at least one trainable encoder layer (the backward starts at the layer loop)"
         # args.pooling (model_bert.py:130-135): 'att' | 'cls' | anything else = mean ; args.model == 'NRMS' puts a
         # nrms_heads x 16 self-attention in front of every user encoder's pooling (model_bert.py:145-148)
         self.pooling = pooling if pooling in ("att", "cls") else "mean"
@@ -161,10 +172,13 @@ def param_shapes(cfg):
 
 
 def is_trainable(cfg, name):
-    """run.py:101-112: teachers frozen; bert_model frozen except encoder.layer[i], i in trainable_layers."""
+    """run.py:101-112: teachers frozen; bert_model frozen except encoder.layer[i], i in trainable_layers (and, an extension the
+    reference does not have, bert.embeddings.* under cfg.train_embeddings; rel_pos_bias, pooler and classifier stay frozen)."""
     if name.startswith("teachers."):
         return False
     if name.startswith(PFX + "bert_model."):
+        if getattr(cfg, "train_embeddings", False) and name.startswith(BERT + "embeddings."):
+            return True
         for l in cfg.trainable_layers:
             if name.startswith(BERT + "encoder.layer.%d." % l):
                 return True
@@ -447,6 +461,7 @@ class Engine:
         if (p_hidden or 0.0) <= 0.0 and (p_attn or 0.0) <= 0.0:
             self.drop = None
             return
+        assert not self.cfg.train_embeddings, "train_embeddings: the engine's embedding backward takes no dropout site (kernel level only)"
         self.drop = dict(p_hidden=float(p_hidden or 0.0), p_attn=float(p_attn or 0.0), seed=int(seed), pass_id=int(pass_id))
         if not hasattr(self, "dyprem"):
             z = lambda *s_: torch.zeros(s_, device=self.dev, dtype=self.tdt)
@@ -471,6 +486,8 @@ class Engine:
         cfg, dev, bf = self.cfg, self.dev, self.tdt
         H, I = cfg.H, cfg.I
         lo = min(cfg.trainable_layers) if cfg.trainable_layers else cfg.n_layers
+        if cfg.train_embeddings:
+            lo = 0           # the gradient runs down to the embeddings: every layer keeps its activations and has transposed copies
         self.lo = lo
         self.sh = []
         for l in range(cfg.n_layers):
@@ -600,6 +617,13 @@ class Engine:
         self.lpart = {l: dict(ln_part=f(T.query("tnr_ln_bwd_part_elems", Mp, H)), ln_part1=f(T.query("tnr_ln_bwd_part_elems", Mp, H)),
                               gcs_part=f(T.query("tnr_gemm_colsum_rows", Mp), I), qkvb_part=f(Nx, 3 * H), cs_tmp=f(I))
                       for l in cfg.trainable_layers}
+        if cfg.train_embeddings:
+            # embedding backward: fp32 gradient rows of the summed embeddings (N L H 4 bytes), its [dgamma | dbeta] partials, the
+            # column-sum partials of the position rows ((N, L H) view) and of the token-type row
+            self.dx_emb = f(Mp, H)
+            self.emb_part = f(T.query("tnr_embed_ln_bwd_part_elems", Mp, H))
+            self.emb_cs_part = f(max(T.query("tnr_colsum_part_elems", max(Nx, 1), L * H), T.query("tnr_colsum_part_elems", L, H),
+                                     T.query("tnr_colsum_part_elems", Mp, H)))
         self.red = {}                                                      # gradient bucket -> _ReduceBatch
         self.cs_part = f(max(T.query("tnr_colsum_part_elems", Mp, 3 * H if L > 32 else QPAD),
                              T.query("tnr_colsum_part_elems", 128, I),
@@ -872,6 +896,7 @@ class Engine:
             T.call("tnr_gather_rows", fc[1], fc[3], nidx, n_seq, self.Lr, 1, self.mask_add, n_seq, 0)
             first = self.lo
         else:
+            self._emb_src = (tok, nidx, n_seq)                # what _embed_bwd addresses the tokens by
             def embed(e, n, r0, s0):
                 if r0:
                     e._embed_fwd(src2[0], n, src2[1], self.x0[r0:])
@@ -1344,16 +1369,62 @@ class Engine:
                     yield (l, "att")
                 if not one:
                     rba.flush()
-            if l > self.lo:
+            if l > self.lo or cfg.train_embeddings:
                 nxt = self.dy2 if dy is self.dy else self.dy
                 self._gemm(self.dqkv, sh["qkvT"], nxt, M, res=self.dh1pre, flags=T.EPI_RES)
                 dy = nxt
             if tr and after_bucket:
                 after_bucket(bucket)
                 bucket += 1
+        if cfg.train_embeddings:
+            assert not two and not defer
+            rbe = rb_heads if one else self.red.setdefault(("emb", form, Ns), _ReduceBatch(self.dev))
+            self._embed_bwd(dy, N, acc, rbe)
+            if not one:
+                rbe.flush()
         if one:
             rb_heads.flush()
+        if cfg.train_embeddings and after_bucket:
+            after_bucket(bucket)           # the embedding block: the last bucket of the step
         self._wg_defer = None
+
+    def _embed_bwd(self, dy, n_seq, acc, rb):
+        """BertEmbeddings backward (tnlrv3/modeling.py:153-178) for the sequences of the last encode(): dy (n_seq L, H) 16-bit =
+        gradient w.r.t. the embedding output at the loss scale -> the gradients of the three tables and of the embedding LayerNorm.
+        tnr_embed_ln_bwd recomputes the forward's rows and leaves fp32 dx at the true scale; the word rows are a fixed-order
+        scatter-sum of dx keyed by token id (row 0 = padding_idx of :138 never gets one), the position rows the column sums of the
+        (n_seq, L H) view, the token-type row 0 the column sums of those.  Keys and order are integer index preparation on the
+        device (like _pos_ids): the token ids of the ENCODED rows - after de-duplication the distinct news, in resident mode
+        gathered from the table by nidx - through a stable sort."""
+        cfg, g, gr = self.cfg, self.p, self.grads
+        L, H = cfg.L, cfg.H
+        E_ = BERT + "embeddings."
+        tok, nidx, n_enc = self._emb_src
+        assert n_enc == n_seq and self.drop_cur is None, "embedding backward: no dropout site, one part"
+        M = n_seq * L
+        args = (n_seq, L, H, dy, g(E_ + "word_embeddings.weight"), g(E_ + "position_embeddings.weight"),
+                g(E_ + "token_type_embeddings.weight"), g(E_ + "LayerNorm.weight"), cfg.ln_eps, self.ginv, self.dx_emb, self.emb_part,
+                None, None)
+        if nidx is None:
+            self._c("tnr_embed_ln_bwd", tok, *args)
+            ids = tok[:n_seq, :L]
+        else:
+            self._c("tnr_embed_ln_bwd_indexed", tok, nidx, *args)
+            ids = tok[nidx[:n_seq].long(), :L]
+        nblk = T.query("tnr_embed_ln_bwd_blocks", M)
+        rb.add(self.emb_part, nblk, 2 * H, 2 * H, self._view(E_ + "LayerNorm.weight", 2 * H, (2 * H,), grad=True), acc, self.ginv)
+        keys, order = torch.sort(ids.reshape(-1).to(torch.int32), stable=True)
+        gw = gr[E_ + "word_embeddings.weight"]
+        if not acc:
+            gw.zero_()                     # rows no token of this step names keep no stale gradient
+        T.call("tnr_scatter_sum_rows", self.dx_emb, M, H, keys, order.to(torch.int32), 0, gw, cfg.vocab, 1)
+        gp = gr[E_ + "position_embeddings.weight"]
+        self._c("tnr_colsum", self.dx_emb, L * H, T.F32, n_seq, L * H, gp, self.emb_cs_part, acc)        # rows >= L get nothing
+        # token-type row 0 = the sum of all dx rows = the column sums of this step's position rows (not of gp: under acc it holds more)
+        if acc:
+            self._c("tnr_colsum", self.dx_emb, H, T.F32, M, H, gr[E_ + "token_type_embeddings.weight"], self.emb_cs_part, 1)
+        else:
+            self._c("tnr_colsum", gp, H, T.F32, L, H, gr[E_ + "token_type_embeddings.weight"], self.emb_cs_part, 0)
 
     def grad(self, name):
         """Gradient of a trainable parameter (a view into flat_g; the fp16 loss scale never reaches it)."""
@@ -1368,6 +1439,9 @@ class Engine:
             e = self.off(names[-1]) + self.slot[names[-1]][2]
             out.append((f0, _rup(e, 64)))          # FFN block: intermediate.dense .. output.LayerNorm
             out.append((a0, f0))                   # attention block: q/k/v .. attention.output.LayerNorm
+        if self.cfg.train_embeddings:              # the embedding block (tables + LayerNorm) completes last
+            last = BERT + "embeddings.LayerNorm.bias"
+            out.append((self.off(BERT + "embeddings.word_embeddings.weight"), _rup(self.off(last) + self.slot[last][2], 64)))
         return out
 
     # ------------------------------------------------------------------ optimiser

@@ -47,7 +47,9 @@ def engine_config_from_args(args, num_teachers=None, is_teacher=False):
         max_pos=cfg.get("max_position_embeddings", 512), type_vocab=cfg.get("type_vocab_size", 2),
         ln_eps=cfg.get("layer_norm_eps", 1e-12), pooling=getattr(args, "pooling", "att"),
         pos_pad_id=cfg.get("pad_token_id", 1) if getattr(args, "tnr_model_type", "tnlrv3") == "roberta" else None,
-        nrms_heads=getattr(args, "num_attention_heads", 0) if getattr(args, "model", "NAML") == "NRMS" else 0)
+        nrms_heads=getattr(args, "num_attention_heads", 0) if getattr(args, "model", "NAML") == "NRMS" else 0,
+        # --train_embeddings: the student's (PLM-NR: the model's) own fine-tuning only, never a frozen teacher encoder
+        train_embeddings=bool(getattr(args, "train_embeddings", False)) and not is_teacher)
 
 
 @torch.no_grad()

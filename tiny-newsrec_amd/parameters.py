@@ -32,6 +32,7 @@ def _flag_table():
     t += [("bert_trainable_layer", int, [], dict(nargs="+", choices=list(range(12)))),
           ("teacher_ckpts", str, [], dict(nargs="+")), ("teacher_emb_paths", str, [], dict(nargs="+")),
           # additions (defaults keep the reference behaviour)
+          ("train_embeddings", _B, False, dict(help="also fine-tune bert.embeddings.* (word / position / token-type tables and the embedding LayerNorm) at the encoder's learning rate; the reference freezes them (run.py:101-112); needs --bert_trainable_layer")),
           ("resident_tables", _B, True, dict(help="keep news_combined / teacher tables in HBM and ship indices only")),
           ("cache_frozen_layers", _B, True, dict(help="resident mode: compute the frozen lower encoder layers once per news instead of every step (identical results)")),
           ("dedup_news", _B, True, dict(help="encode each distinct news of a batch once (resident mode; identical results)")),
@@ -49,6 +50,8 @@ def build_parser():
     ap = argparse.ArgumentParser()
     for f in _FLAGS:
         kw = dict(f[3]) if len(f) > 3 else {}
+        if f[0] == "freeze_embedding":
+            kw["help"] = "parsed and ignored, exactly as in the reference (nothing reads it there); the embeddings are frozen unless --train_embeddings True"
         ap.add_argument("--" + f[0], type=f[1], default=f[2], **kw)
     return ap
 

@@ -55,6 +55,10 @@ def train(args):
         E.Engine.WGRAD_UNITS = 2
     model = ModelBert(args) if plmnr else Model(args)
     eng = model.engine
+    for index in eng.cfg.trainable_layers:                                   # run.py:108
+        logging.info(f"finetune block {index}")
+    if eng.cfg.train_embeddings:
+        logging.info("finetune embeddings")
     sd = model.state_dict()
     pretrained = False
     if args.synthetic:
@@ -196,6 +200,7 @@ def _forward_engine(args, n_layers, sd, add_prefix=""):
     from model_bert import engine_config_from_args
     a = types.SimpleNamespace(**vars(args))
     a.num_student_layers, a.bert_trainable_layer = n_layers, []
+    a.train_embeddings = False
     cfg = engine_config_from_args(a, num_teachers=0)
     eng = E.Engine(cfg, "cuda:%d" % torch.cuda.current_device(), max_batch=args.batch_size, dtype=getattr(args, "dtype", "fp16"))
     src = {add_prefix + k: v for k, v in sd.items()}

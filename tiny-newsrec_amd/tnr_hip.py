@@ -95,6 +95,10 @@ _SIG = {
     "tnr_relpos_table": [_P, _I, _I, _P, _P],
     "tnr_embed_ln_fwd": [_P, _L, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P],
     "tnr_embed_ln_fwd_indexed": [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P],
+    "tnr_embed_ln_bwd": [_P, _L, _I, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _D, _P, _P],
+    "tnr_embed_ln_bwd_indexed": [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _D, _P, _P],
+    "tnr_embed_ln_bwd_part_elems": [_L, _I],
+    "tnr_embed_ln_bwd_blocks": [_L],
     "tnr_gemm_nt": [_P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _P, _L, _P, _L, _I, _P],
     "tnr_gemm_nt_ex": [_P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _P, _L, _P, _L, _I, _P, _P],
     "tnr_gemm_colsum_rows": [_L],
@@ -137,6 +141,7 @@ _SIG = {
     "tnr_concat_i32": [_P, _L, _P, _L, _P, _P],
     "tnr_gather_rows": [_P, _L, _P, _L, _I, _I, _P, _L, _L, _P],
     "tnr_segment_sum_rows": [_P, _P, _P, _L, _I, _P, _P],
+    "tnr_scatter_sum_rows": [_P, _L, _I, _P, _P, _I, _P, _L, _I, _P],
     "tnr_user_score_fwd": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "tnr_user_bwd_pre": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "tnr_user_bwd_post": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P],
@@ -164,7 +169,7 @@ _SIG = {
     "tnr_cast_bf16_to_f32": [_P, _P, _L, _P],
 }
 # entry points that exist twice: bf16 (plain name) and fp16 (suffix _f16)
-TYPED = ["tnr_embed_ln_fwd", "tnr_embed_ln_fwd_indexed", "tnr_gemm_nt", "tnr_gemm_nt_ex", "tnr_gemm_colsum_rows", "tnr_gemm_nt_route",
+TYPED = ["tnr_embed_ln_fwd", "tnr_embed_ln_fwd_indexed", "tnr_embed_ln_bwd", "tnr_embed_ln_bwd_indexed", "tnr_gemm_nt", "tnr_gemm_nt_ex", "tnr_gemm_colsum_rows", "tnr_gemm_nt_route",
          "tnr_gemm_tn_wgrad", "tnr_gemm_tn_wgrad_ex", "tnr_gemm_tn_wgrad_group", "tnr_gemm_tn_ws_elems", "tnr_ln_fwd", "tnr_ln_bwd", "tnr_attn_l32_fwd", "tnr_attn_l32_bwd", "tnr_attn_long_fwd", "tnr_attn_long_bwd",
          "tnr_colsum", "tnr_colsum_batched", "tnr_attpool_fwd", "tnr_attpool_bwd", "tnr_attpool_fwd_long", "tnr_attpool_bwd_long", "tnr_attpool_long_ws_elems", "tnr_refresh_shadows",
          "tnr_cast_f32_to_bf16", "tnr_cast_bf16_to_f32", "tnr_pool_fwd", "tnr_pool_bwd"]
@@ -180,7 +185,7 @@ _SIG["tnr_ln_bwd_do_split"] = _SIG["tnr_ln_bwd_do"][:-1] + [_D, _L, _P]
 TYPED += ["tnr_gemm_nt_do", "tnr_ln_bwd_do", "tnr_gemm_nt_do_split", "tnr_ln_bwd_do_split"]
 for _n in TYPED:
     _SIG[_n + "_f16"] = _SIG[_n]
-_RET = {"tnr_attpool_long_ws_elems": _L, "tnr_attpool_long_ws_elems_f16": _L, "tnr_gemm_tn_ws_elems": _L, "tnr_gemm_tn_ws_elems_f16": _L, "tnr_gemm_colsum_rows_f16": _L, "tnr_gemm_colsum_rows": _L, "tnr_ln_bwd_part_elems": _L, "tnr_ln_bwd_blocks": _L, "tnr_colsum_part_elems": _L,
+_RET = {"tnr_attpool_long_ws_elems": _L, "tnr_attpool_long_ws_elems_f16": _L, "tnr_gemm_tn_ws_elems": _L, "tnr_gemm_tn_ws_elems_f16": _L, "tnr_gemm_colsum_rows_f16": _L, "tnr_gemm_colsum_rows": _L, "tnr_ln_bwd_part_elems": _L, "tnr_ln_bwd_blocks": _L, "tnr_embed_ln_bwd_part_elems": _L, "tnr_embed_ln_bwd_blocks": _L, "tnr_colsum_part_elems": _L,
         "tnr_user_bwd_part_stride": _L}
 EXPORTS = sorted(_SIG) + ["tnr_last_error"]
 
