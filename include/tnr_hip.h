@@ -337,7 +337,13 @@ int tnr_user_score_fwd(const float* vec, int64_t R, const int32_t* hidx, const i
  *   tnr_user_bwd_pre : hv (B*U, D) = blended history rows in position order ; dpre (B*U, Q) = gradient of the fc1
  *                      pre-activation ; part (B, 2Q + D + 1) = per-impression partials [b1 | w2 | pad | b2]
  *   caller           : dW1 (Q,D) = dpre^T hv ;  dhv (B*U, D) = dpre W1
- *   tnr_user_bwd_post: dvec[hidx[b,u]] += (alpha * duser + dhv) * m ; fills the pad_doc partial of `part`. */
+ *   tnr_user_bwd_post: dvec[hidx[b,u]] += (alpha * duser + dhv) * m ; fills the pad_doc partial of `part`.
+ * Rows of dvec (the contract of tnr_user_bwd_post, tnr_user_blend_bwd and tnr_score_bwd alike): one workgroup per impression
+ * adds into dvec with plain loads and stores, so the rows named by DIFFERENT impressions must be distinct - a row shared by two
+ * impressions is a race.  A row named more than once WITHIN one impression is fine: each thread walks its impression's slots
+ * serially, the repeats are summed in slot order.  Callers whose impressions share rows (in-batch de-duplication) pass slot
+ * indices (hidx / cidx = arange over the slots of a gathered table) and fold the slot gradients with tnr_segment_sum_rows
+ * afterwards, as tiny-newsrec_amd/engine.py does. */
 int tnr_user_bwd_pre(const float* vec, const int32_t* hidx, const float* mask, const float* pad, const float* w2,
                      int user_log_mask, const float* duser, const float* e, const float* alpha, float* hv,
                      float* dpre, float* part, int B, int U, int D, int Q, void* stream);
@@ -351,7 +357,8 @@ int64_t tnr_user_bwd_part_stride(int D, int Q);
  *   caller             : qkv (n_model, B*U, 3*Dh) = hv [W_Q;W_K;W_V]^T + b   (tnr_sgemm), Dh = n_heads*16
  *   tnr_nrms_attn_fwd  : ctx (n_model, B*U, Dh) ; sc = exp(q.k/4) [* mask_j if use_mask] / (sum + 1e-8), raw exp (:51-58)
  *   tnr_nrms_attn_bwd  : dctx (B*U, Dh) -> dqkv (B*U, 3*Dh) for one model, recomputing sc (two fixed-order phases)
- *   tnr_user_blend_bwd : dvec[hidx] += dhv * m ; pad_part[b*part_stride + d] = sum_u dhv * (1-m) */
+ *   tnr_user_blend_bwd : dvec[hidx] += dhv * m ; pad_part[b*part_stride + d] = sum_u dhv * (1-m)
+ *                        (rows of different impressions distinct, repeats within one summed in slot order: see tnr_user_bwd_post) */
 int tnr_user_blend_fwd(const float* vec, int64_t R, const int32_t* hidx, const float* mask, const float* pad,
                        int user_log_mask, float* hv, int n_model, int B, int U, int D, void* stream);
 int tnr_user_blend_bwd(const float* dhv, const float* mask, const int32_t* hidx, int user_log_mask, float* dvec,
@@ -362,7 +369,9 @@ int tnr_nrms_attn_bwd(const float* qkv, const float* mask, int use_mask, const f
                       int U, int n_heads, void* stream);
 
 /* backward of the scorer bmm (model_bert.py:204): dvec[cidx[b,c]] += dscore[b,c]*user[b] ;
- * duser[b] += sum_c dscore[b,c]*vec[cidx[b,c]] */
+ * duser[b] += sum_c dscore[b,c]*vec[cidx[b,c]].  Rows cidx names in different impressions must be distinct, repeats within one
+ * impression are summed in slot order (see tnr_user_bwd_post); callers with shared rows gather to slots first and fold with
+ * tnr_segment_sum_rows. */
 int tnr_score_bwd(const float* vec, const int32_t* cidx, const float* user, const float* dscore, float* dvec,
                   float* duser, int B, int C, int D, void* stream);
 
