@@ -110,6 +110,9 @@ int64_t tnr_embed_ln_bwd_blocks(int64_t n_tok);              /* partial rows (nb
 /* C[M,N] = epilogue(A[M,K] . B[N,K]^T).  bf16 operands, fp32 MFMA accumulation.
  * Forward Linear (tnlrv3/modeling.py:236-248, transformers BertSelfOutput/BertIntermediate/BertOutput),
  * and its dgrad when B is the transposed weight copy.  N % 128 == 0, K % 64 == 0, any M >= 1.
+ * Only rows [0, M) of A, res and aux are ever used (a row tile that hangs over M re-reads row M - 1; what lies behind it in the
+ * buffers is the caller's and may hold anything), and only rows [0, M) x columns [0, N) of C and of the TNR_EPI_AUXOUT output are
+ * written: with a leading dimension above the width the gap columns keep their contents, in the operands they are never read.
  * Streams and threads: every entry point enqueues on `stream` and returns; calls may come from any thread.  The
  * persistent 256-column kernel hands its tiles out from a small counter block the library keeps per (device, stream) and
  * that the last workgroup of a launch zeroes again - launches of one stream are ordered, so each finds it zeroed; launches
@@ -164,7 +167,9 @@ int tnr_gemm_clock_stamps(void* buf, int64_t n_pairs);
 
 /* dW[N,K] (fp32) = dY[M,N]^T . X[M,K] : weight gradient of a Linear.  Reduction over M is split into
  * `splits` slabs in `ws` (fp32, splits*N*K elements) and summed in fixed order (deterministic).
- * Rows [M, Mpad) of dY and X must be zero, Mpad = roundup(M, 64) ; N % 128 == 0, K % 128 == 0.
+ * Rows [M, Mpad) of dY and X must be zero, Mpad = roundup(M, 64) ; N % 128 == 0, K % 128 == 0.  Rows at and behind Mpad are never
+ * read, nor are gap columns (lddy > N, ldx > K); gap columns of dW (lddw > K) keep their contents.  `splits` is clamped to the number
+ * of 64-row tiles and then to the number of non-empty splits: slabs of `ws` past that count are not touched.
  * accumulate != 0 adds into dW.  _ex: dW (+)= out_scale * dY^T X (the fp16 build's backward runs on loss-scaled
  * gradients; 1 / scale is applied here so that parameter gradients are the true ones, run.py:194). */
 int tnr_gemm_tn_wgrad(const void* dY, int64_t lddy, const void* X, int64_t ldx, float* dW, int64_t lddw,

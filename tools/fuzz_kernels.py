@@ -73,7 +73,7 @@ for case in range(n_cases // 3):
     N = int(rs.choice([128, 256, 768, 2304])); K = int(rs.choice([128, 256, 768, 3072]))
     Mp = (M + 63) // 64 * 64
     dy = torch.zeros((Mp, N), device=dev, dtype=dt); dy[:M] = (torch.randn((M, N), device=dev) * 0.5).to(dt)
-    x = torch.full((Mp, K), 9.0, device=dev, dtype=dt); x[:M] = (torch.randn((M, K), device=dev) * 0.5).to(dt)     # pad rows of x need not be zero
+    x = torch.full((Mp, K), 9.0, device=dev, dtype=dt); x[:M] = (torch.randn((M, K), device=dev) * 0.5).to(dt)     # include/tnr_hip.h requires zero pad rows in BOTH operands; X's are filled here to see that dY's zeros alone already cancel them - callers must not rely on it
     splits = int(rs.choice([1, 2, 3, 7, 16]))
     ws = torch.zeros(T.query("tnr_gemm_tn_ws_elems" + sfx, N, K, splits), device=dev)
     acc = int(rs.rand() < 0.3)
