@@ -199,14 +199,19 @@ typedef struct {
 } tnr_wgrad_problem_t;
 int tnr_gemm_tn_wgrad_group(const tnr_wgrad_problem_t* problems, int n, void* stream);
 
-/* LayerNorm over the last dim (H % 256 == 0), eps inside the sqrt (torch.nn.LayerNorm).
- * fwd: y = LN(x) ; stats (M,2) fp32 = (mean, rstd) kept for backward. */
+/* LayerNorm over the last dim (H = 256, 512, 768 or 1024), eps inside the sqrt (torch.nn.LayerNorm).
+ * fwd: y = LN(x) ; stats (M,2) fp32 = (mean, rstd) kept for backward, or NULL: y alone, the same bits.
+ * Forward and backward read only rows [0, M) of x, dy and stats and write only rows [0, M) of y, dx and dxm. */
 int tnr_ln_fwd(const void* x, const float* gamma, const float* beta, float eps, void* y, float* stats,
                int64_t M, int H, void* stream);
 /* bwd: dx = LN'(dy) ; partial sums go to part (nblk,3,H) fp32 then are reduced into dgamma, dbeta and
  * dxsum = column sums of dx (the bias gradient of the Linear in front of this LayerNorm); each may be null.
- * With all three null and part given, only the partials (nblk = ceil(M/128) rows of [dgamma|dbeta|dxsum]) are
- * written and the caller reduces them (tnr_reduce_multi). */
+ * With all three null and part given, only the partials (exactly nblk = tnr_ln_bwd_blocks(M) rows of [dgamma|dbeta|dxsum]:
+ * 32 rows of x per partial row below M = 32768, 128 from there on) are written and the caller reduces them
+ * (tnr_reduce_multi); the rest of the workspace is left alone.
+ * The call forms: all three sums ; dgamma and dbeta adjacent (dbeta == dgamma + H: one reduction for both) ; all three null
+ * with part ; any one of the three alone ; part null (then all three must be null): dx only.  dx is the same bits in every form.
+ * When a sum is requested, part is scratch: the reduction may overwrite it.  dxsum sums the ROUNDED 16-bit dx. */
 int tnr_ln_bwd(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
                float* dgamma, float* dbeta, float* dxsum, float* part, int64_t M, int H, void* stream);
 int64_t tnr_ln_bwd_part_elems(int64_t M, int H);   /* workspace good for every row count <= M */
@@ -231,7 +236,9 @@ int tnr_attn_long_fwd(const void* qkv, const float* mask_add, const float* rel, 
 int tnr_attn_long_bwd(const void* qkv, const float* mask_add, const float* rel, const void* ctx, const void* dctx,
                       const float* lse, float* delta, void* dqkv, int64_t n_seq, int L, int A, void* stream);
 
-/* column sums (bias gradients): out[n] (+)= sum_m X[m,n] ; X bf16 or fp32 (dtype) ; part (nblk,N) fp32 */
+/* column sums (bias gradients): out[n] (+)= sum_m X[m,n] ; X bf16 or fp32 (dtype) ; part (nblk,N) fp32 scratch.
+ * N % 4 == 0, ldx % 4 == 0, ldx >= N.  Only [0, M) x [0, N) of X is read: never a gap column (N .. ldx), a row behind M
+ * or, batched, the space between two matrices. */
 int tnr_colsum(const void* X, int64_t ldx, int dtype, int64_t M, int64_t N, float* out, float* part,
                int accumulate, void* stream);
 /* batch of matrices X + z*sX -> out (batch, N) ; part needs batch * tnr_colsum_part_elems(M, N) */
@@ -242,7 +249,8 @@ int64_t tnr_colsum_part_elems(int64_t M, int64_t N);
 /* ---- heads ----------------------------------------------------------------------------------- */
 
 /* AttentionPooling over the L tokens of each title, no mask (model_bert.py:15-34 called at :133).
- * e (N*L, lde) fp32 = tanh(fc1 y) from tnr_gemm_nt (padded columns must be 0) ; w2 (Q) ; b2 scalar.
+ * e (N*L, lde) fp32 = tanh(fc1 y) from tnr_gemm_nt ; w2 (Q) ; b2 scalar.  Forward and backward, in both forms, read only the
+ * columns q < Q of e (the GEMM that writes e leaves zeros in its padded columns; these kernels do not depend on it).
  * out: nv (N,H) fp32, alpha (N,Lr) fp32 normalised weights (Lr = roundup(L,32), L <= 512), den (N) fp32 = sum exp + 1e-8. */
 int tnr_attpool_fwd(const void* y, const float* e, int64_t lde, const float* w2, const float* b2, int Q,
                     float* nv, float* alpha, float* den, int64_t n_seq, int L, int H, void* stream);
@@ -487,7 +495,8 @@ int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, float* v, float
 
 /* refresh bf16 weight copies after an update: desc = n_desc * 8 int64 on DEVICE:
  * {src fp32 ptr, rows, cols, dst ptr (or 0), dst ld, dstT ptr (or 0), dstT ld, unused}
- * dst[r*ld + c] = bf16(src[r,c]) ; dstT[c*ldT + r] = bf16(src[r,c]). */
+ * dst[r*ld + c] = bf16(src[r,c]) ; dstT[c*ldT + r] = bf16(src[r,c]), round to nearest even.  Only [0, rows) x [0, cols) of
+ * each copy is written (ld >= cols, ldT >= rows: the gap columns keep what they held). */
 int tnr_refresh_shadows(const int64_t* desc, int n_desc, int64_t total_tiles, const int64_t* tile_start,
                         void* stream);
 

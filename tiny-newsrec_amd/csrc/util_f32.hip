@@ -136,6 +136,7 @@ extern "C" int64_t tnr_embed_ln_bwd_blocks(int64_t n_tok) { return embwd_blocks(
 extern "C" int tnr_reduce_rows(const float* part, int64_t rows, int64_t stride, int64_t n, float* out, int accumulate,
                                void* stream) {
     TNR_CHECK_ARG(part && out && rows >= 1 && n >= 1, "tnr_reduce_rows: bad argument");
+    // (tests/rows_ref.py::reduce_rows_depth restates this branching for its error bounds: retune the two together)
     const int64_t colblk = (n + 63) / 64;
     if (n < 64 && rows >= 256) {
         hipLaunchKernelGGL(reduce_rows_narrow_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, part, rows,
