@@ -13,6 +13,7 @@ kernel after each update, activations of the trainable layers stay resident for 
 import logging
 import math
 import struct
+from types import SimpleNamespace
 
 import torch
 
@@ -307,6 +308,7 @@ class Engine:
         self.tdt = torch.float16 if self.f16 else torch.bfloat16
         self._gbase = LOSS_SCALE if self.f16 else 1.0
         self.cfg, self.dev = cfg, torch.device(device)
+        self.lnames = [layer_param_order(l) for l in range(cfg.n_layers)]     # formatted once: the layer blocks of every step look them up
         # dynamic loss scale (fp16 only); engines that share parameters share it (stage 1: both passes of a step use one scale)
         self.scaler = share.scaler if share is not None else LossScaler(self.dev, self.f16)
         self.step_count = 0
@@ -463,7 +465,7 @@ class Engine:
             return
         assert not self.cfg.train_embeddings, "train_embeddings: the engine's embedding backward takes no dropout site (kernel level only)"
         self.drop = dict(p_hidden=float(p_hidden or 0.0), p_attn=float(p_attn or 0.0), seed=int(seed), pass_id=int(pass_id))
-        if not hasattr(self, "dyprem"):
+        if self.dyprem is None:
             z = lambda *s_: torch.zeros(s_, device=self.dev, dtype=self.tdt)
             self.dyprem, self.dh1prem = z(self.Mp, self.cfg.H), z(self.Mp, self.cfg.H)
 
@@ -574,7 +576,7 @@ class Engine:
         self.nv, self.alpha, self.den = f(Nx, H), f(N, Lr), f(N)
         Rt = N + B
         self.Rt = Rt
-        if hasattr(self, "dyprem"):
+        if self.dyprem is not None:
             self.dyprem, self.dh1prem = z(Mp, H), z(Mp, H)
         self.S = f(Rt, D)                 # student rows: [B*U history | B*C candidate | B user]
         self.dS = f(Rt, D)
@@ -656,6 +658,15 @@ class Engine:
                          # data-parallel case, where a workgroup held off its CU by a collective costs a quarter of what it costs now
     _wg = None           # the collected weight gradients while a layer's backward runs
     _wg_defer = None     # ... while a backward runs step by step beside another engine's (backward_encoder_steps)
+    sg_kdiv = 256        # K per split of the small fp32 GEMMs (_sgemm_problem; 128 was 0.3 % slower: `AB=sg_kdiv:128:256 tools/step_ab.py`)
+    group_sgemm = True   # False: the independent fp32 GEMMs of the heads one tnr_sgemm each (_sgemm_group; `AB=group_sgemm:0:1 tools/step_ab.py`)
+    fused_user_fwd = True    # False: fc1 of the user encoders as fp32 GEMMs in front of tnr_user_score_fwd, four launches more per pass (EXPERIMENTS.md, tools/scratch/uf_time.py)
+    teacher_stream = None    # a torch.cuda.Stream: the teacher side of the forward on it; no gain measured (`AB=teacher_stream:0:1 tools/step_ab.py`)
+    fcache = None        # build_frozen_cache(): (hidden states entering layer lo, additive masks, the table's address, its rows) per news
+    _pos_cache = None    # _pos_ids(): (key, position ids) of the resident token table
+    _red_ginv = None     # _red_check(): the 1 / (loss scale) the recorded reduction tables carry
+    dyprem = dh1prem = None  # set_dropout(): the masked LayerNorm-backward outputs, allocated by the first call that turns dropout on
+    nr_s = nr_t = None   # _alloc_workspace() under nrms_heads: the student's / teachers' (blended rows, q|k|v, [ctx | candidates])
 
     @staticmethod
     def _wgrad_splits(N, K, units=None):
@@ -718,26 +729,29 @@ class Engine:
 
     def _sgemm(self, A, a_rs, a_cs, sA, Bm, b_rs, b_cs, sB, C, ldc, sC, bias, sBias, M, N, K, batch=1, ksplit=None, alpha=1.0,
                beta=0.0):
-        """ksplit None: K is split into slices of >= 256 (a workgroup's time on the fp32 MFMA is ~K * 32 cycles whatever the
-        tile count, and these GEMMs have few tiles; slices of 128 cost a split-reduce launch for the K = 256 GEMMs and were 0.3 %
-        slower on the step, `AB=sg_kdiv:128:256 tools/step_ab.py`).  The split depends on K ALONE, never on the row count: a news vector must
-        come out with the same bits whatever batch it is encoded in (in-batch de-duplication, frozen-layer cache)."""
-        if ksplit is None:
-            ksplit = max(1, min(K // getattr(self, "sg_kdiv", 256), 8))
-            assert ksplit * batch * M * N <= self.sg_part.numel(), "fp32 GEMM workspace too small for its K split"
-        T.call("tnr_sgemm", A, a_rs, a_cs, sA, None, Bm, b_rs, b_cs, sB, C, ldc, sC, bias, sBias, M, N, K, batch, alpha, beta,
-               ksplit, self.sg_part if ksplit > 1 else None)
+        """One fp32 GEMM in a launch of its own (tnr_sgemm); a K split takes its partial sums through self.sg_part."""
+        self._sgemm_call(self._sgemm_problem(A, a_rs, a_cs, sA, Bm, b_rs, b_cs, sB, C, ldc, sC, bias, sBias, M, N, K, batch, ksplit,
+                                             alpha, beta, part=self.sg_part))
 
     def _sgemm_problem(self, A, a_rs, a_cs, sA, Bm, b_rs, b_cs, sB, C, ldc, sC, bias, sBias, M, N, K, batch=1, ksplit=None, alpha=1.0,
                        beta=0.0, part=None):
         """The arguments of _sgemm as one member of a grouped launch (T.sgemm_group: independent small GEMMs in one launch, each
-        computed exactly as its own tnr_sgemm call would).  A split problem needs a partial buffer of its own (`part`)."""
+        computed exactly as its own tnr_sgemm call would).  A split problem needs a partial buffer of its own (`part`).
+        ksplit None: K is split into slices of >= sg_kdiv = 256 (a workgroup's time on the fp32 MFMA is ~K * 32 cycles whatever the
+        tile count, and these GEMMs have few tiles; slices of 128 cost a split-reduce launch for the K = 256 GEMMs and were 0.3 %
+        slower on the step, `AB=sg_kdiv:128:256 tools/step_ab.py`).  The split depends on K ALONE, never on the row count: a news vector must
+        come out with the same bits whatever batch it is encoded in (in-batch de-duplication, frozen-layer cache)."""
         if ksplit is None:
-            ksplit = max(1, min(K // getattr(self, "sg_kdiv", 256), 8))
+            ksplit = max(1, min(K // self.sg_kdiv, 8))
         if ksplit > 1 and part is not None:
             assert ksplit * batch * M * N <= part.numel(), "fp32 GEMM workspace too small for its K split"
         return dict(A=A, a_rs=a_rs, a_cs=a_cs, sA=sA, B=Bm, b_rs=b_rs, b_cs=b_cs, sB=sB, C=C, ldc=ldc, sC=sC, bias=bias, sBias=sBias,
                     M=M, N=N, K=K, batch=batch, alpha=alpha, beta=beta, ksplit=ksplit, part=part if ksplit > 1 else None)
+
+    def _sgemm_call(self, q):
+        """A problem of _sgemm_problem as its own tnr_sgemm launch: the one place that spells the entry point's argument order."""
+        T.call("tnr_sgemm", q["A"], q["a_rs"], q["a_cs"], q["sA"], None, q["B"], q["b_rs"], q["b_cs"], q["sB"], q["C"], q["ldc"], q["sC"],
+               q["bias"], q["sBias"], q["M"], q["N"], q["K"], q["batch"], q["alpha"], q["beta"], q["ksplit"], q["part"])
 
     def _sgemm_group(self, problems):
         """Independent fp32 GEMMs in one launch (Engine.group_sgemm = False: one tnr_sgemm each, the same bits; tools/step_ab.py).
@@ -752,12 +766,11 @@ class Engine:
         assert off <= self.sg_part.numel(), "fp32 GEMM workspace too small for the K splits of a grouped launch"
         parts = [q["part"].data_ptr() for q in problems if q["part"] is not None]
         assert len(parts) == len(set(parts)), "two members of a grouped fp32 GEMM share a partial buffer"
-        if getattr(self, "group_sgemm", True):
+        if self.group_sgemm:
             T.sgemm_group(problems)
             return
         for q in problems:
-            T.call("tnr_sgemm", q["A"], q["a_rs"], q["a_cs"], q["sA"], None, q["B"], q["b_rs"], q["b_cs"], q["sB"], q["C"], q["ldc"], q["sC"],
-                   q["bias"], q["sBias"], q["M"], q["N"], q["K"], q["batch"], q["alpha"], q["beta"], q["ksplit"], q["part"])
+            self._sgemm_call(q)
 
     # ------------------------------------------------------------------ forward
     def build_frozen_cache(self, news_combined):
@@ -786,7 +799,7 @@ class Engine:
         """RoBERTa position ids of a token table (rows [ids | mask], any integer dtype) -> (rows, L) int32; the resident table's
         are computed once (cached by its address).  Integer index preparation, like the torch.cat of the news indices."""
         key = (tok.data_ptr(), tuple(tok.shape))
-        c = getattr(self, "_pos_cache", None)
+        c = self._pos_cache
         if c is not None and c[0] == key:
             return c[1]
         L, pad = self.cfg.L, self.cfg.pos_pad_id
@@ -809,6 +822,17 @@ class Engine:
         else:
             _fork_join(side, lambda: fn(*parts[1]), lambda: fn(*parts[0]))
 
+    def _parts_state(self, parts, N, side, **more):
+        """What the launches of one encode() / backward over `parts` share, built once per call (a plain record, no behaviour)."""
+        two = len(parts) > 1
+        return SimpleNamespace(
+            parts=parts, side=side, two=two, N=N,
+            M0=N * self.cfg.L,                                # rows of the first part: where a second one's begin
+            M=sum(n * e.cfg.L for e, n, _, _ in parts), Ns=sum(n for _, n, _, _ in parts),
+            ds=self._dsite,                                   # dropout sites of this part's current forward call (self.drop_cur)
+            ds2=parts[1][0]._dsite if two else None,          # ... and of the second part's, for the rows from M0 on (_gemm, _ln_bwd)
+            **more)
+
     def _embed_fwd(self, tok, n_seq, nidx, x0):
         cfg, g, ds = self.cfg, self.p, self._dsite
         L, H = cfg.L, cfg.H
@@ -817,52 +841,41 @@ class Engine:
                g(BERT + "embeddings.LayerNorm.bias"), cfg.ln_eps, x0, self.mask_add)
         de = ds(T.DROP_EMB, 0)
         pid = self._pos_ids(tok if nidx is not None else tok[:n_seq]) if cfg.pos_pad_id is not None else None
-        if nidx is None:
-            self._c("tnr_embed_ln_fwd_do", tok, n_seq, L, H, *emb, de, pid) if (de or pid is not None) else \
-                self._c("tnr_embed_ln_fwd", tok, n_seq, L, H, *emb)
-        else:
-            self._c("tnr_embed_ln_fwd_indexed_do", tok, nidx, n_seq, L, H, *emb, de, pid) if (de or pid is not None) else \
-                self._c("tnr_embed_ln_fwd_indexed", tok, nidx, n_seq, L, H, *emb)
+        name, args = ("tnr_embed_ln_fwd", (tok, n_seq, L, H, *emb)) if nidx is None else \
+            ("tnr_embed_ln_fwd_indexed", (tok, nidx, n_seq, L, H, *emb))
+        self._c(name + "_do", *args, de, pid) if (de or pid is not None) else self._c(name, *args)
 
     def _attn_fwd(self, qkv, ctx, lse, n_seq, dp):
         cfg = self.cfg
-        if cfg.L <= 32:
-            if dp:
-                self._c("tnr_attn_l32_fwd_do", qkv, self.mask_add, self.rel, ctx, n_seq, cfg.L, cfg.A, dp)
-            else:
-                self._c("tnr_attn_l32_fwd", qkv, self.mask_add, self.rel, ctx, n_seq, cfg.L, cfg.A)
-        else:
-            largs = (qkv, self.mask_add, self.rel, ctx, lse, n_seq, cfg.L, cfg.A)
-            self._c("tnr_attn_long_fwd_do", *largs, dp) if dp else self._c("tnr_attn_long_fwd", *largs)
+        name, args = ("tnr_attn_l32_fwd", (qkv, self.mask_add, self.rel, ctx, n_seq, cfg.L, cfg.A)) if cfg.L <= 32 else \
+            ("tnr_attn_long_fwd", (qkv, self.mask_add, self.rel, ctx, lse, n_seq, cfg.L, cfg.A))
+        self._c(name + "_do", *args, dp) if dp else self._c(name, *args)
 
     def _attpool_fwd(self, x, e, nv, n_seq):
         cfg, g = self.cfg, self.p
+        args = (x, e, QPAD, g(PFX + "attn.att_fc2.weight"), g(PFX + "attn.att_fc2.bias"), cfg.Qn, nv, self.alpha, self.den)
         if cfg.L > AP_LONG:                  # few, long sequences (stage-1 bodies): the chunked kernels fill the chip
-            self._c("tnr_attpool_fwd_long", x, e, QPAD, g(PFX + "attn.att_fc2.weight"), g(PFX + "attn.att_fc2.bias"), cfg.Qn,
-                    nv, self.alpha, self.den, self.ap_ws, n_seq, cfg.L, cfg.H)
+            self._c("tnr_attpool_fwd_long", *args, self.ap_ws, n_seq, cfg.L, cfg.H)
         else:
-            self._c("tnr_attpool_fwd", x, e, QPAD, g(PFX + "attn.att_fc2.weight"), g(PFX + "attn.att_fc2.bias"), cfg.Qn,
-                    nv, self.alpha, self.den, n_seq, cfg.L, cfg.H)
+            self._c("tnr_attpool_fwd", *args, n_seq, cfg.L, cfg.H)
 
     def _attpool_bwd(self, y, e, dnv, dy2, dpre, dw2p, db2p, db1p, n_seq):
         cfg, g = self.cfg, self.p
+        args = (y, e, QPAD, g(PFX + "attn.att_fc2.weight"), cfg.Qn, dnv, self.alpha)
+        outs = (dy2, dpre, QPAD, dw2p, db2p, db1p)
         if cfg.L > AP_LONG:
-            self._c("tnr_attpool_bwd_long", y, e, QPAD, g(PFX + "attn.att_fc2.weight"), cfg.Qn, dnv, self.alpha,
-                    dy2, dpre, QPAD, dw2p, db2p, db1p, self.ap_ws, n_seq, cfg.L, cfg.H)
+            self._c("tnr_attpool_bwd_long", *args, *outs, self.ap_ws, n_seq, cfg.L, cfg.H)
         else:
-            self._c("tnr_attpool_bwd", y, e, QPAD, g(PFX + "attn.att_fc2.weight"), cfg.Qn, dnv, self.alpha, self.den,
-                    dy2, dpre, QPAD, dw2p, db2p, db1p, n_seq, cfg.L, cfg.H)
+            self._c("tnr_attpool_bwd", *args, self.den, *outs, n_seq, cfg.L, cfg.H)
 
     def _attn_bwd(self, qkv, ctx, lse, dctx, dqkv, qkvb_part, n_seq, dPb):
         """-> True if the q/k/v bias partial sums came out of the kernel (L <= 32), False if the caller sums dqkv's columns."""
         cfg = self.cfg
-        if cfg.L <= 32:
-            bargs = (qkv, self.mask_add, self.rel, dctx, dqkv, qkvb_part, n_seq, cfg.L, cfg.A)
-            self._c("tnr_attn_l32_bwd_do", *bargs, dPb) if dPb else self._c("tnr_attn_l32_bwd", *bargs)
-            return True
-        bargs = (qkv, self.mask_add, self.rel, ctx, dctx, lse, self.delta, dqkv, n_seq, cfg.L, cfg.A)
-        self._c("tnr_attn_long_bwd_do", *bargs, dPb) if dPb else self._c("tnr_attn_long_bwd", *bargs)
-        return False
+        short = cfg.L <= 32
+        name, args = ("tnr_attn_l32_bwd", (qkv, self.mask_add, self.rel, dctx, dqkv, qkvb_part, n_seq, cfg.L, cfg.A)) if short else \
+            ("tnr_attn_long_bwd", (qkv, self.mask_add, self.rel, ctx, dctx, lse, self.delta, dqkv, n_seq, cfg.L, cfg.A))
+        self._c(name + "_do", *args, dPb) if dPb else self._c(name, *args)
+        return short
 
     def encode(self, tok, n_seq, nidx=None, out=None, stop_at=None, train=True, extra=None, parts=None, src2=None, side=None,
                before=None):
@@ -873,22 +886,14 @@ class Engine:
         launches behind this one's, their news vectors to S[n_seq:]; side = the stream of its own kernels or None; before() is
         called directly in front of this part's embedding launch (work of the caller's that runs beside the part behind)."""
         cfg = self.cfg
-        H = cfg.H
-        parts = parts or [(self, n_seq, 0, 0)]
-        two = len(parts) > 1
-        M0 = n_seq * cfg.L                                    # rows of the first part: where a second one's begin
-        M = sum(n * e.cfg.L for e, n, _, _ in parts)
-        Ns = sum(n for _, n, _, _ in parts)
-        assert M <= self.Mp and Ns <= self.nv.shape[0]
-        g = self.p
-        for e, _, _, _ in parts:
+        s = self._parts_state(parts or [(self, n_seq, 0, 0)], n_seq, side)
+        assert s.M <= self.Mp and s.Ns <= self.nv.shape[0]
+        for e, _, _, _ in s.parts:
             if e._rel_stale:
                 e.refresh_rel()
             e._begin_drop_call(train)                         # each part its own numbered forward call
-        ds = self._dsite
-        ds2 = parts[1][0]._dsite if two else None             # ... and the second part's, for the rows from M0 on (_gemm)
-        fc = getattr(self, "fcache", None) if self.drop_cur is None else None      # a cached prefix has no fresh masks
-        assert not two or (fc is None and stop_at is None and out is None and not extra and cfg.pooling == "att")
+        fc = self.fcache if self.drop_cur is None else None   # a cached prefix has no fresh masks
+        assert not s.two or (fc is None and stop_at is None and out is None and not extra and cfg.pooling == "att")
         first = 0
         if fc is not None and nidx is not None and stop_at is None and tok.data_ptr() == fc[2]:
             # frozen prefix from the per-news cache (build_frozen_cache): two row gathers replace embedding + lo layers
@@ -904,49 +909,59 @@ class Engine:
                 if before:
                     before()
                 e._embed_fwd(tok, n, nidx, self.x0)
-            self._per_part(parts, side, embed)
+            self._per_part(s.parts, side, embed)
         x = self.x0
         self.x_in = {}
         for l in range(first, cfg.n_layers):
             if stop_at is not None and l == stop_at:
                 return x
-            names = layer_param_order(l)
-            sh = self.sh[l]
-            kept = l >= self.lo
-            a = self.act[l - self.lo] if kept else self.scr
-            y = a["y"] if kept else self.scr_y[l & 1]
-            bqkv = self._view(names[3], 3 * H, (3 * H,))
-            self.x_in[l] = x
-            self._gemm(x, sh["qkv"], a["qkv"], M, bias=bqkv, flags=T.EPI_BIAS)
-
-            def attn(e, n, r0, s0):
-                e._attn_fwd(_from(a["qkv"], r0), _from(a["ctx"], r0), e.act[l - e.lo]["lse"] if kept else e.lse, n,
-                            e._dsite(T.DROP_PROB, l))
-            self._per_part(parts, side, attn)
-            self._gemm(a["ctx"], sh["o"], a["h1pre"], M, bias=g(names[7]), res=x, flags=T.EPI_BIAS | T.EPI_RES,
-                       drop=ds(T.DROP_ATTN_OUT, l), drop_tail=ds2(T.DROP_ATTN_OUT, l) if two else None, split_row=M0)
-            self._c("tnr_ln_fwd", a["h1pre"], g(names[8]), g(names[9]), cfg.ln_eps, a["h1"], a["st1"], M, H)
-            fl = T.EPI_BIAS | T.EPI_GELU | (T.EPI_AUXOUT if kept else 0)
-            self._gemm(a["h1"], sh["w1"], a["g"], M, bias=g(names[11]), aux=a["u"] if kept else None, flags=fl)
-            self._gemm(a["g"], sh["w2"], a["ypre"], M, bias=g(names[13]), res=a["h1"], flags=T.EPI_BIAS | T.EPI_RES,
-                       drop=ds(T.DROP_FFN_OUT, l), drop_tail=ds2(T.DROP_FFN_OUT, l) if two else None, split_row=M0)
-            self._c("tnr_ln_fwd", a["ypre"], g(names[14]), g(names[15]), cfg.ln_eps, y, a["st2"], M, H)
-            x = y
+            x = self._layer_fwd(s, l, x)
         self.y_last = x
-        # pooling (model_bert.py:130-135: AttentionPooling without mask | token 0 | mean) + dense (:136)
+        return self._head_fwd(s, x, out, extra)
+
+    def _layer_fwd(self, s, l, x):
+        """Encoder layer l (tnlrv3/modeling.py BertLayer): x -> y.  A layer from lo on keeps its activations for the backward (and its
+        input in x_in); a frozen one below works in the scratch set and alternates between the two scratch outputs."""
+        cfg, g, ds, ds2 = self.cfg, self.p, s.ds, s.ds2
+        H, M = cfg.H, s.M
+        names, sh = self.lnames[l], self.sh[l]
+        kept = l >= self.lo
+        a = self.act[l - self.lo] if kept else self.scr
+        y = a["y"] if kept else self.scr_y[l & 1]
+        self.x_in[l] = x
+        self._gemm(x, sh["qkv"], a["qkv"], M, bias=self._view(names[3], 3 * H, (3 * H,)), flags=T.EPI_BIAS)
+
+        def attn(e, n, r0, s0):
+            e._attn_fwd(_from(a["qkv"], r0), _from(a["ctx"], r0), e.act[l - e.lo]["lse"] if kept else e.lse, n,
+                        e._dsite(T.DROP_PROB, l))
+        self._per_part(s.parts, s.side, attn)
+        self._gemm(a["ctx"], sh["o"], a["h1pre"], M, bias=g(names[7]), res=x, flags=T.EPI_BIAS | T.EPI_RES,
+                   drop=ds(T.DROP_ATTN_OUT, l), drop_tail=ds2(T.DROP_ATTN_OUT, l) if s.two else None, split_row=s.M0)
+        self._c("tnr_ln_fwd", a["h1pre"], g(names[8]), g(names[9]), cfg.ln_eps, a["h1"], a["st1"], M, H)
+        fl = T.EPI_BIAS | T.EPI_GELU | (T.EPI_AUXOUT if kept else 0)
+        self._gemm(a["h1"], sh["w1"], a["g"], M, bias=g(names[11]), aux=a["u"] if kept else None, flags=fl)
+        self._gemm(a["g"], sh["w2"], a["ypre"], M, bias=g(names[13]), res=a["h1"], flags=T.EPI_BIAS | T.EPI_RES,
+                   drop=ds(T.DROP_FFN_OUT, l), drop_tail=ds2(T.DROP_FFN_OUT, l) if s.two else None, split_row=s.M0)
+        self._c("tnr_ln_fwd", a["ypre"], g(names[14]), g(names[15]), cfg.ln_eps, y, a["st2"], M, H)
+        return y
+
+    def _head_fwd(self, s, x, out, extra):
+        """Pooling (model_bert.py:130-135: AttentionPooling without mask | token 0 | mean) + dense (:136) of the news encoder:
+        the last layer's output x -> news vectors in `out` (None: self.S)."""
+        cfg, g = self.cfg, self.p
+        H = cfg.H
         if cfg.pooling == "att":
-            self._gemm(x, self.sh_a1, self.e, M, bias=self.b_a1, flags=T.EPI_BIAS | T.EPI_TANH | T.EPI_OUTF32)
-            self._per_part(parts, side, lambda e, n, r0, s0: e._attpool_fwd(_from(x, r0), _from(self.e, r0), _from(self.nv, s0), n))
+            self._gemm(x, self.sh_a1, self.e, s.M, bias=self.b_a1, flags=T.EPI_BIAS | T.EPI_TANH | T.EPI_OUTF32)
+            self._per_part(s.parts, s.side, lambda e, n, r0, s0: e._attpool_fwd(_from(x, r0), _from(self.e, r0), _from(self.nv, s0), n))
         else:
-            self._c("tnr_pool_fwd", x, self.nv, n_seq, cfg.L, H, int(cfg.pooling == "mean"))
-        wd = g(PFX + "dense.weight")
+            self._c("tnr_pool_fwd", x, self.nv, s.N, cfg.L, H, int(cfg.pooling == "mean"))
         dst = self.S if out is None else out
-        dense = (self.nv, H, 1, 0, wd, H, 1, 0, dst, cfg.D, 0, g(PFX + "dense.bias"), 0, Ns, cfg.D, H)
+        dense = (self.nv, H, 1, 0, g(PFX + "dense.weight"), H, 1, 0, dst, cfg.D, 0, g(PFX + "dense.bias"), 0, s.Ns, cfg.D, H)
         if extra:      # independent fp32 GEMMs the caller had pending (the teachers' projection): one launch with the dense layer
             self._sgemm_group([self._sgemm_problem(*dense)] + list(extra))
         else:
             self._sgemm(*dense)
-        return dst[:Ns]
+        return dst[:s.Ns]
 
     # ------------------------------------------------------------------ forward-only paths (SURVEY 8-f N2)
     @torch.no_grad()
@@ -976,7 +991,7 @@ class Engine:
         hidx = self.hidx[:B]
         mask = history_mask.to(torch.float32).contiguous()
         self._user_forward(rows, B * U, 1, self._user_params(ue, 1), hidx, hidx, mask, self.epre_u, self.dS, B * D, self.score,
-                           self.e_u, self.alpha_u, self.den_u, B, 0, getattr(self, "nr_s", None))
+                           self.e_u, self.alpha_u, self.den_u, B, 0, self.nr_s)
         return self.dS[:B].clone()
 
     def _prepare(self, B):
@@ -1032,7 +1047,7 @@ class Engine:
                         self.X[i, B * U:N].copy_(teacher_cand[i].reshape(B * C, D))
                 self._user_forward(self.X, self.X.shape[1], T_, self._user_params("teachers.0.", T_), hidx, cidx, self.mask,
                                    self.epre_t, self.X[0, N:], self.X.stride(0), self.t_score, self.e_t, self.alpha_t,
-                                   self.den_t, B, C, getattr(self, "nr_t", None))
+                                   self.den_t, B, C, self.nr_t)
                 Wt = self._view("transform_matrix.0.weight", T_ * D * D, (T_, D, D))
                 bt = self._view("transform_matrix.0.bias", T_ * D, (T_, D))
                 proj = (self.X, D, 1, self.X.stride(0), Wt, D, 1, D * D, self.Pm, D, self.Pm.stride(0), bt, D, Rt, D, D)
@@ -1062,7 +1077,7 @@ class Engine:
         g = self.p
         Qu = cfg.Qu
         self._user_forward(S, Rt, 1, self._user_params("student.user_encoder.", 1), hidx, cidx, self.mask, self.epre_u, S[N:],
-                           B * D, self.score, self.e_u, self.alpha_u, self.den_u, B, C, getattr(self, "nr_s", None))
+                           B * D, self.score, self.e_u, self.alpha_u, self.den_u, B, C, self.nr_s)
         if T_ > 0:
             main.wait_stream(side)
         T.call("tnr_kd_score_loss", self.score, self.t_score if T_ else None, self.label, cfg.temperature, cfg.coef,
@@ -1092,7 +1107,7 @@ class Engine:
         cfg = self.cfg
         U, D, Qu, ulm = cfg.U, cfg.D, cfg.Qu, int(cfg.user_log_mask)
         if not cfg.nrms_heads:
-            if getattr(self, "fused_user_fwd", True) and D % 8 == 0 and 4 * (64 * (D + 4) + U * Qu + 64 + D) <= 160 * 1024:
+            if self.fused_user_fwd and D % 8 == 0 and 4 * (64 * (D + 4) + U * Qu + 64 + D) <= 160 * 1024:
                 # fc1 inside the kernel: one launch per pass (was: batched fp32 GEMM + split reduce + fc1(pad) pair + this kernel)
                 T.call("tnr_user_score_fwd", vec, R, hidx, cidx, mask, p["pad"], p["w1"], p["b1"], p["w2"], p["b2"], ulm, None, None,
                        user, user_stride, score, e, alpha, den, nm, B, U, C, D, Qu)
@@ -1123,8 +1138,7 @@ class Engine:
     def _side_stream(self):
         # measured on MI355X (A/B on one box): no gain from a real second stream for the teacher side, so it shares
         # the main one (Engine.teacher_stream = a torch.cuda.Stream to opt in)
-        side = getattr(self, "teacher_stream", None)
-        return side if side is not None else torch.cuda.current_stream(self.dev)
+        return self.teacher_stream if self.teacher_stream is not None else torch.cuda.current_stream(self.dev)
 
     def _idx(self, B):
         assert B == self.B_alloc
@@ -1139,7 +1153,7 @@ class Engine:
     def _red_check(self):
         """The batched reductions replay a recorded job table that carries 1 / (loss scale) in its descriptors: when the dynamic
         scale has moved since they were recorded (an fp16 overflow, a growth step) they are recorded afresh."""
-        if getattr(self, "_red_ginv", None) != self.ginv:
+        if self._red_ginv != self.ginv:
             self.red.clear()
             self._red_ginv = self.ginv
 
@@ -1239,47 +1253,33 @@ class Engine:
         two passes over the same parameters in step can launch both passes' contributions to a weight as ONE chained problem.
         parts, side: as in the encode() this backward belongs to; dvec then holds both parts' rows.  Two parts always write
         (acc = 0, no defer), collect a layer's weight gradients if group_wgrad (None: self.group_wgrad) and launch them with one
-        round shared by all of them (_wgrad_flush)."""
+        round shared by all of them (_wgrad_flush).
+        This is the protocol with the caller only - which partial sums are reduced when, where the weight gradients leave, the
+        yields and the bucket hook; the kernels are in the block methods below, called in the order of the launches."""
         cfg = self.cfg
         self._red_check()
         parts = parts or [(self, N, 0, 0)]
         two = len(parts) > 1
         assert not two or (acc == 0 and not defer and cfg.pooling == "att")
         self._wg_defer = [] if defer else None
-        D, H, I = cfg.D, cfg.H, cfg.I
-        M0 = N * cfg.L                      # rows of the first part: where a second one's begin
-        M = sum(n * e.cfg.L for e, n, _, _ in parts)
-        Ns = sum(n for _, n, _, _ in parts)
-        group = (self.group_wgrad if group_wgrad is None else group_wgrad) and not defer
-        g, gr = self.p, self.grads
         self._wg = None                    # nothing collected from an earlier, interrupted backward
-        ds = self._dsite                   # sites of the forward call this backward belongs to (self.drop_cur)
-        ds2 = parts[1][0]._dsite if two else None      # ... and of the second part's, for the rows from M0 on
-        gi = self.ginv                     # parameter gradients below the pooling backward: 1 / loss scale on the way out
-        # no bucket hook (one GPU): every partial sum of the backward in ONE batched reduction at its end
+        group = (self.group_wgrad if group_wgrad is None else group_wgrad) and not defer
+        # q / k / v bias: the short-sequence attention backward leaves one partial row per sequence, the long one none (its dqkv
+        # columns are summed into ONE row): the parts' rows one behind the other in qkvb_part, one reduction job over all of them
+        s = self._parts_state(parts, N, side, acc=acc, qrows=[n if e.cfg.L <= 32 else 1 for e, n, _, _ in parts],
+                              gi=self.ginv)        # parameter gradients below the pooling backward: 1 / loss scale on the way out
+        s.nblk = T.query("tnr_ln_bwd_blocks", s.M)
+        # no bucket hook (one GPU): nothing waits for any bucket, so every partial sum of the backward - heads, layers, embeddings -
+        # goes into ONE batched reduction at its end; otherwise a batch per gradient bucket, flushed where the bucket completes
         one = after_bucket is None and self.merge_reductions
         # the recorded reduction tables of one pass (writing or adding) and of two parts never replay each other's
         form = "joint" if two else acc
-        rb = rb_heads = self.red.setdefault(("heads", form, Ns, one), _ReduceBatch(self.dev))
-        # dense + pooling of the news encoder
-        wd = g(PFX + "dense.weight")
-        self._sgemm_group(list(pend or []) + [
-            self._sgemm_problem(dvec, 1, D, 0, self.nv, 1, H, 0, gr[PFX + "dense.weight"], H, 0, None, 0, D, H, Ns, ksplit=self.KS,
-                                beta=float(acc)),
-            self._sgemm_problem(dvec, D, 1, 0, wd, 1, H, 0, self.dnv, H, 0, None, 0, Ns, H, D, alpha=self.gscale)])   # loss scale enters here
-        rb.add(dvec, Ns, D, D, gr[PFX + "dense.bias"], acc)       # column sums; in place, behind the two GEMMs that read dvec
-        y = self.y_last
-        if cfg.pooling == "att":
-            self._per_part(parts, side, lambda e, n, r0, s0: e._attpool_bwd(
-                _from(y, r0), _from(self.e, r0), _from(self.dnv, s0), _from(self.dy2, r0), _from(self.dpre, r0), _from(self.dw2p, s0),
-                _from(self.db2p, s0), _from(self.db1p, s0), n))
-            rb.add(self.dw2p, Ns, cfg.Qn, cfg.Qn, gr[PFX + "attn.att_fc2.weight"], acc, gi)
-            rb.add(self.db2p, Ns, 1, 1, gr[PFX + "attn.att_fc2.bias"], acc, gi)
-            rb.add(self.db1p, Ns, QPAD, QPAD, self._view(PFX + "attn.att_fc1.bias", QPAD, (QPAD,), grad=True), acc, gi)
+        rb_heads = self.red.setdefault(("heads", form, s.Ns, one), _ReduceBatch(self.dev))
+        batch = lambda *key: rb_heads if one else self.red.setdefault(key, _ReduceBatch(self.dev))
+        self._head_bwd_pool(s, dvec, pend, rb_heads)
         if not one or not cfg.trainable_layers:
-            rb.flush()
-        if cfg.pooling == "att":
-            self._wgrad(self.dpre, y, self._view(PFX + "attn.att_fc1.weight", QPAD * H, (QPAD, H), grad=True), M, acc)
+            rb_heads.flush()
+        self._head_bwd_wgrad(s)
         if defer:
             yield "heads"
         if after_bucket:
@@ -1287,52 +1287,17 @@ class Engine:
         if not cfg.trainable_layers:
             self._wg_defer = None
             return
-        if cfg.pooling == "att":
-            self._gemm(self.dpre, self.sh_a1T, self.dy, M, res=self.dy2, flags=T.EPI_RES)
-        else:
-            self._c("tnr_pool_bwd", self.dnv, self.dy, N, cfg.L, H, int(cfg.pooling == "mean"))
-        dy = self.dy
+        dy = self._head_bwd_dgrad(s)
         bucket = 1
-        nblk = T.query("tnr_ln_bwd_blocks", M)
-        # q / k / v bias: the short-sequence attention backward leaves one partial row per sequence, the long one none (its dqkv
-        # columns are summed into ONE row): the parts' rows one behind the other in qkvb_part, one reduction job over all of them
-        qrows = [n if e.cfg.L <= 32 else 1 for e, n, _, _ in parts]
         for l in range(cfg.n_layers - 1, self.lo - 1, -1):
-            names, sh, a = layer_param_order(l), self.sh[l], self.act[l - self.lo]
-            tr = l in cfg.trainable_layers
-            x_in = self.x_in[l]
-            # bias gradients ride along: dx column sums from LayerNorm backward, the dgrad epilogue, attention backward;
-            # all partial sums of the layer are reduced by one launch at the end (fixed order)
             # two gradient buckets per layer, in completion order: the FFN block (names[10:16]) is final after the W1
             # weight gradient, the attention block (names[0:10]) at the end of the layer -- the last all-reduce of a step
             # (attention block of layer lo) is then a third of a layer instead of a whole one
-            # (without a bucket hook - one GPU - nothing waits for any bucket: the partial sums of all layers and of the heads go
-            # into one batched reduction at the end of the backward)
+            tr = l in cfg.trainable_layers
             self._wg = [] if (tr and group) else None
-            rba = (rb_heads if one else self.red.setdefault((l, form, Ns, "att"), _ReduceBatch(self.dev))) if tr else None
-            rb = (rb_heads if one else self.red.setdefault((l, form, Ns, "ffn"), _ReduceBatch(self.dev))) if tr else None
-            P = self.lpart.get(l)
-            # with dropout behind the two output Linears the LayerNorm backward has two outputs: dx for the residual branch and
-            # dx * mask / (1 - p) = the Linear's output gradient (its weight gradient, dgrad and -- through the partials -- bias)
-            dF, dO = ds(T.DROP_FFN_OUT, l), ds(T.DROP_ATTN_OUT, l)
-            dypre_lin = self.dyprem if dF else self.dypre
-            dh1pre_lin = self.dh1prem if dO else self.dh1pre
-            self._ln_bwd((dy, a["ypre"], a["st2"], g(names[14]), self.dypre, None, None, None, (P["ln_part"] if tr else None), M, H),
-                         dypre_lin, dF, ds2(T.DROP_FFN_OUT, l) if two else None, M0)
+            rba, rb = (batch(l, form, s.Ns, "att"), batch(l, form, s.Ns, "ffn")) if tr else (None, None)
+            self._ffn_bwd(s, l, dy, rb)
             if tr:
-                rb.add(P["ln_part"], nblk, 3 * H, 2 * H, self._view(names[14], 2 * H, (2 * H,), grad=True), acc, gi)   # [dgamma | dbeta]
-                rb.add(P["ln_part"][2 * H:], nblk, 3 * H, H, gr[names[13]], acc, gi)                                 # output.dense.bias
-                self._wgrad(dypre_lin, a["g"], gr[names[12]], M, acc)
-            fused_cs = tr and M > 128            # the column-sum epilogue needs more than one 128-row strip (a toy batch has less)
-            self._gemm(dypre_lin, sh["w2T"], self.du, M, aux=a["u"], flags=T.EPI_MULDGELU | (T.EPI_COLSUM if fused_cs else 0),
-                       colsum=P["gcs_part"] if fused_cs else None)
-            if tr:
-                if fused_cs:
-                    rb.add(P["gcs_part"], self._q("tnr_gemm_colsum_rows", M), I, I, gr[names[11]], acc, gi)
-                else:
-                    self._c("tnr_colsum", self.du, I, T.BF16, M, I, P["cs_tmp"][:I], self.cs_part, 0)
-                    rb.add(P["cs_tmp"], 1, I, I, gr[names[11]], acc, gi)
-                self._wgrad(self.du, a["h1"], gr[names[10]], M, acc)
                 if not one:
                     rb.flush()
                 if defer and split_ffn:
@@ -1342,26 +1307,8 @@ class Engine:
                         self._wgrad_flush(two)         # the FFN block's two gradients: its bucket goes out now
                     after_bucket(bucket)
                     bucket += 1
-            self._gemm(self.du, sh["w1T"], self.dh1, M, res=self.dypre, flags=T.EPI_RES)
-            self._ln_bwd((self.dh1, a["h1pre"], a["st1"], g(names[8]), self.dh1pre, None, None, None, (P["ln_part1"] if tr else None), M, H),
-                         dh1pre_lin, dO, ds2(T.DROP_ATTN_OUT, l) if two else None, M0)
+            self._att_bwd(s, l, rba)
             if tr:
-                rba.add(P["ln_part1"], nblk, 3 * H, 2 * H, self._view(names[8], 2 * H, (2 * H,), grad=True), acc, gi)
-                rba.add(P["ln_part1"][2 * H:], nblk, 3 * H, H, gr[names[7]], acc, gi)                               # attention.output.dense.bias
-                self._wgrad(dh1pre_lin, a["ctx"], gr[names[6]], M, acc)
-            self._gemm(dh1pre_lin, sh["oT"], self.dctx, M)
-            qp = P["qkvb_part"] if tr else None
-
-            def attn(e, n, r0, s0):
-                q0 = qrows[0] if r0 else 0             # the part's first row of qkvb_part
-                dqkv = _from(self.dqkv, r0)
-                if not e._attn_bwd(_from(a["qkv"], r0), _from(a["ctx"], r0), e.act[l - e.lo]["lse"], _from(self.dctx, r0), dqkv,
-                                   _from(qp, q0) if tr else None, n, e._dsite(T.DROP_PROB, l)) and tr:
-                    e._c("tnr_colsum", dqkv, 3 * H, T.BF16, n * e.cfg.L, 3 * H, qp[q0], e.cs_part, 0)
-            self._per_part(parts, side, attn)
-            if tr:
-                rba.add(qp, sum(qrows), 3 * H, 3 * H, self._view(names[3], 3 * H, (3 * H,), grad=True), acc, gi)
-                self._wgrad(self.dqkv, x_in, self._view(names[0], 3 * H * H, (3 * H, H), grad=True), M, acc)
                 if self._wg is not None:               # all four of the layer (two under a bucket hook), before the next layer overwrites their operands
                     self._wgrad_flush(two)
                     self._wg = None
@@ -1370,15 +1317,13 @@ class Engine:
                 if not one:
                     rba.flush()
             if l > self.lo or cfg.train_embeddings:
-                nxt = self.dy2 if dy is self.dy else self.dy
-                self._gemm(self.dqkv, sh["qkvT"], nxt, M, res=self.dh1pre, flags=T.EPI_RES)
-                dy = nxt
+                dy = self._qkv_dgrad(l, dy, s.M)
             if tr and after_bucket:
                 after_bucket(bucket)
                 bucket += 1
         if cfg.train_embeddings:
             assert not two and not defer
-            rbe = rb_heads if one else self.red.setdefault(("emb", form, Ns), _ReduceBatch(self.dev))
+            rbe = batch("emb", form, s.Ns)
             self._embed_bwd(dy, N, acc, rbe)
             if not one:
                 rbe.flush()
@@ -1387,6 +1332,107 @@ class Engine:
         if cfg.train_embeddings and after_bucket:
             after_bucket(bucket)           # the embedding block: the last bucket of the step
         self._wg_defer = None
+
+    # The blocks of the backward, in launch order: the news head in the three pieces the driver's flush and yield cut it into, then
+    # per layer the FFN block, the attention block and the dgrad into the layer below.  s: the record of _parts_state; rb: the
+    # reduction batch of the block's gradient bucket (None for a layer that is not trainable: it only passes the gradient on).
+    # Bias and LayerNorm gradients ride along as partial sums - dx column sums from LayerNorm backward, the dgrad epilogue, attention
+    # backward - registered with rb.add and reduced by the driver's flush (fixed order).
+    def _head_bwd_pool(self, s, dvec, pend, rb):
+        """Dense + pooling of the news encoder: dvec -> dnv; attention pooling: -> dpre (fc1's output gradient) and dy2 (the pooled
+        sum's share of the last layer's output gradient)."""
+        cfg, g, gr, acc, Ns = self.cfg, self.p, self.grads, s.acc, s.Ns
+        D, H = cfg.D, cfg.H
+        self._sgemm_group(list(pend or []) + [
+            self._sgemm_problem(dvec, 1, D, 0, self.nv, 1, H, 0, gr[PFX + "dense.weight"], H, 0, None, 0, D, H, Ns, ksplit=self.KS,
+                                beta=float(acc)),
+            self._sgemm_problem(dvec, D, 1, 0, g(PFX + "dense.weight"), 1, H, 0, self.dnv, H, 0, None, 0, Ns, H, D,
+                                alpha=self.gscale)])      # loss scale enters here
+        rb.add(dvec, Ns, D, D, gr[PFX + "dense.bias"], acc)       # column sums; in place, behind the two GEMMs that read dvec
+        if cfg.pooling == "att":
+            y = self.y_last
+            self._per_part(s.parts, s.side, lambda e, n, r0, s0: e._attpool_bwd(
+                _from(y, r0), _from(self.e, r0), _from(self.dnv, s0), _from(self.dy2, r0), _from(self.dpre, r0), _from(self.dw2p, s0),
+                _from(self.db2p, s0), _from(self.db1p, s0), n))
+            rb.add(self.dw2p, Ns, cfg.Qn, cfg.Qn, gr[PFX + "attn.att_fc2.weight"], acc, s.gi)
+            rb.add(self.db2p, Ns, 1, 1, gr[PFX + "attn.att_fc2.bias"], acc, s.gi)
+            rb.add(self.db1p, Ns, QPAD, QPAD, self._view(PFX + "attn.att_fc1.bias", QPAD, (QPAD,), grad=True), acc, s.gi)
+
+    def _head_bwd_wgrad(self, s):
+        if self.cfg.pooling == "att":
+            H = self.cfg.H
+            self._wgrad(self.dpre, self.y_last, self._view(PFX + "attn.att_fc1.weight", QPAD * H, (QPAD, H), grad=True), s.M, s.acc)
+
+    def _head_bwd_dgrad(self, s):
+        """-> dy, the gradient w.r.t. the last layer's output."""
+        cfg = self.cfg
+        if cfg.pooling == "att":
+            self._gemm(self.dpre, self.sh_a1T, self.dy, s.M, res=self.dy2, flags=T.EPI_RES)
+        else:
+            self._c("tnr_pool_bwd", self.dnv, self.dy, s.N, cfg.L, cfg.H, int(cfg.pooling == "mean"))
+        return self.dy
+
+    def _ffn_bwd(self, s, l, dy, rb):
+        """Layer l from the second LayerNorm's backward to the W1 weight gradient: dy -> dypre (residual branch), du."""
+        cfg, g, gr, acc, gi, M = self.cfg, self.p, self.grads, s.acc, s.gi, s.M
+        H, I = cfg.H, cfg.I
+        names, sh, a, P = self.lnames[l], self.sh[l], self.act[l - self.lo], self.lpart.get(l)
+        tr = rb is not None
+        # with dropout behind the two output Linears the LayerNorm backward has two outputs: dx for the residual branch and
+        # dx * mask / (1 - p) = the Linear's output gradient (its weight gradient, dgrad and -- through the partials -- bias)
+        dF = s.ds(T.DROP_FFN_OUT, l)
+        dypre_lin = self.dyprem if dF else self.dypre
+        self._ln_bwd((dy, a["ypre"], a["st2"], g(names[14]), self.dypre, None, None, None, (P["ln_part"] if tr else None), M, H),
+                     dypre_lin, dF, s.ds2(T.DROP_FFN_OUT, l) if s.two else None, s.M0)
+        if tr:
+            rb.add(P["ln_part"], s.nblk, 3 * H, 2 * H, self._view(names[14], 2 * H, (2 * H,), grad=True), acc, gi)   # [dgamma | dbeta]
+            rb.add(P["ln_part"][2 * H:], s.nblk, 3 * H, H, gr[names[13]], acc, gi)                                 # output.dense.bias
+            self._wgrad(dypre_lin, a["g"], gr[names[12]], M, acc)
+        fused_cs = tr and M > 128            # the column-sum epilogue needs more than one 128-row strip (a toy batch has less)
+        self._gemm(dypre_lin, sh["w2T"], self.du, M, aux=a["u"], flags=T.EPI_MULDGELU | (T.EPI_COLSUM if fused_cs else 0),
+                   colsum=P["gcs_part"] if fused_cs else None)
+        if tr:
+            if fused_cs:
+                rb.add(P["gcs_part"], self._q("tnr_gemm_colsum_rows", M), I, I, gr[names[11]], acc, gi)
+            else:
+                self._c("tnr_colsum", self.du, I, T.BF16, M, I, P["cs_tmp"][:I], self.cs_part, 0)
+                rb.add(P["cs_tmp"], 1, I, I, gr[names[11]], acc, gi)
+            self._wgrad(self.du, a["h1"], gr[names[10]], M, acc)
+
+    def _att_bwd(self, s, l, rb):
+        """Layer l from the W1 dgrad to the QKV weight gradient: du, dypre -> dh1pre (residual branch), dqkv."""
+        cfg, g, gr, acc, gi, M = self.cfg, self.p, self.grads, s.acc, s.gi, s.M
+        H = cfg.H
+        names, sh, a, P = self.lnames[l], self.sh[l], self.act[l - self.lo], self.lpart.get(l)
+        tr = rb is not None
+        dO = s.ds(T.DROP_ATTN_OUT, l)
+        dh1pre_lin = self.dh1prem if dO else self.dh1pre
+        self._gemm(self.du, sh["w1T"], self.dh1, M, res=self.dypre, flags=T.EPI_RES)
+        self._ln_bwd((self.dh1, a["h1pre"], a["st1"], g(names[8]), self.dh1pre, None, None, None, (P["ln_part1"] if tr else None), M, H),
+                     dh1pre_lin, dO, s.ds2(T.DROP_ATTN_OUT, l) if s.two else None, s.M0)
+        if tr:
+            rb.add(P["ln_part1"], s.nblk, 3 * H, 2 * H, self._view(names[8], 2 * H, (2 * H,), grad=True), acc, gi)
+            rb.add(P["ln_part1"][2 * H:], s.nblk, 3 * H, H, gr[names[7]], acc, gi)                               # attention.output.dense.bias
+            self._wgrad(dh1pre_lin, a["ctx"], gr[names[6]], M, acc)
+        self._gemm(dh1pre_lin, sh["oT"], self.dctx, M)
+        qp, qrows = (P["qkvb_part"] if tr else None), s.qrows
+
+        def attn(e, n, r0, s0):
+            q0 = qrows[0] if r0 else 0             # the part's first row of qkvb_part
+            dqkv = _from(self.dqkv, r0)
+            if not e._attn_bwd(_from(a["qkv"], r0), _from(a["ctx"], r0), e.act[l - e.lo]["lse"], _from(self.dctx, r0), dqkv,
+                               _from(qp, q0) if tr else None, n, e._dsite(T.DROP_PROB, l)) and tr:
+                e._c("tnr_colsum", dqkv, 3 * H, T.BF16, n * e.cfg.L, 3 * H, qp[q0], e.cs_part, 0)
+        self._per_part(s.parts, s.side, attn)
+        if tr:
+            rb.add(qp, sum(qrows), 3 * H, 3 * H, self._view(names[3], 3 * H, (3 * H,), grad=True), acc, gi)
+            self._wgrad(self.dqkv, self.x_in[l], self._view(names[0], 3 * H * H, (3 * H, H), grad=True), M, acc)
+
+    def _qkv_dgrad(self, l, dy, M):
+        """The gradient handed to the layer below: dqkv, dh1pre -> whichever of dy / dy2 layer l's own input gradient `dy` is not."""
+        nxt = self.dy2 if dy is self.dy else self.dy
+        self._gemm(self.dqkv, self.sh[l]["qkvT"], nxt, M, res=self.dh1pre, flags=T.EPI_RES)
+        return nxt
 
     def _embed_bwd(self, dy, n_seq, acc, rb):
         """BertEmbeddings backward (tnlrv3/modeling.py:153-178) for the sequences of the last encode(): dy (n_seq L, H) 16-bit =

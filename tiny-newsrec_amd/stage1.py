@@ -10,18 +10,20 @@ for the weighted sum is evaluated as the stacked product it intends (oracle/news
 that reading against the notebook's own modules).
 
 One model, two sequence lengths: two Engine instances share parameters / gradients / optimiser state / 16-bit
-weight copies and own their workspaces.  Their backwards run in step, layer by layer: the bias / LayerNorm sums of the title pass
-are written and those of the body pass added; every weight gradient is ONE chained problem over the title rows and the body rows
-(tnr_gemm_tn_wgrad_group, accumulate = 2).
-Round 6 - JOINT passes (`Stage1Engine.joint`, the default, with dropout or without): a Linear, a LayerNorm and a weight gradient act on token
+weight copies and own their workspaces.
+JOINT passes (`Stage1Engine.joint`, the default, with dropout or without): a Linear, a LayerNorm and a weight gradient act on token
 rows one by one, so the body pass's rows are laid directly BEHIND the title pass's in every per-token buffer and each of them is
 ONE launch over M = N Lt + B Lb rows instead of one per pass (8 896 rows at 30 / 128, 24 064 at 24 / 512: tile orders large enough
 for the persistent 256-wide kernels); only what depends on the sequence length - embeddings, attention, pooling - still runs per
 pass, on its row range (one stream: `joint_streams` puts the body's on a second one, measured slower).  A layer's four weight
 gradients leave in ONE grouped persistent launch whose units share one round (Engine._wgrad_flush, shared_round).  There is no layer
-loop here: Engine.encode and Engine.backward_encoder_steps work on a list of parts of the host engine's buffers, one for a single
-pass, and this class only hands them two - [(title, N, 0, 0), (body, B, N Lt, N)], the title engine as host (`_parts`).  The per-pass
-forms (`joint` off, or a configuration `_joint_ok` refuses) call the same two functions once per engine.
+loop here: Engine.encode and Engine.backward_encoder_steps run the engine's per-block methods over a list of parts of the host
+engine's buffers, one for a single pass, and this class only hands them two - [(title, N, 0, 0), (body, B, N Lt, N)], the title
+engine as host (`_parts`).
+The per-pass forms (`joint` off, or a configuration `_joint_ok` refuses) call the same two functions once per engine.  Chained
+(`chain_wgrad`, their default): the two backwards run in step, block by block (backward_encoder_steps as a generator) - the bias /
+LayerNorm sums of the title pass are written and those of the body pass added; every weight gradient is ONE chained problem over the
+title rows and the body rows (tnr_gemm_tn_wgrad_group, accumulate = 2; `_wgrad_flush_chained`).
 Every row goes through the same K order as in its own
 launch: scores and losses are bit-identical to the two-launch form; parameter gradients are the same sums in another order.
 With dropout on, each pass keeps its own forward-call number and sites: the two output Linears and the LayerNorm backwards behind
@@ -166,17 +168,19 @@ class Stage1Engine:
                             # Measured (interleaved legs, one box): 1.816 -> 1.718 ms at 30 / 128 and 3.830 -> 3.717 at 24 / 512 WITHOUT it -
                             # ten fork / join pairs per step cost more than running two short kernels side by side wins
     joint_group_wgrad = True    # the joint passes' weight gradients of a layer in ONE persistent launch + one slab sum
+    _side = None            # _side_stream(): the second stream (two_streams, joint_streams), made when first asked for
+    _joint_rows_written = False     # _joint_ok(): the last step laid body rows behind the title engine's own
 
     def _joint_ok(self):
         t, b = self.title, self.body
         cfg = self.cfg_t
         same = lambda d: None if d is None else (d["p_hidden"], d["p_attn"], d["seed"])
         ok = bool(self.joint and same(t.drop) == same(b.drop) and cfg.pooling == "att" and self.dev.type == "cuda"
-                  and getattr(t, "fcache", None) is None and t.group_wgrad is False
+                  and t.fcache is None and t.group_wgrad is False
                   # the grouped weight gradients that share one round (Engine._wgrad_flush) take 256 x 256 tiles only (an
                   # inter = 128 * odd config runs per pass instead)
                   and (not self.joint_group_wgrad or (cfg.H % 256 == 0 and cfg.I % 256 == 0)))
-        if not ok and getattr(self, "_joint_rows_written", False):
+        if not ok and self._joint_rows_written:
             # a per-pass step after joint ones (a tools/ A/B, `joint` switched off): the title engine's own kernels rely on ZERO rows
             # behind its N Lt rows (the weight gradient reads up to the next multiple of 64), where the joint passes have put body
             # rows - lay the title workspace out afresh, once
@@ -185,7 +189,7 @@ class Stage1Engine:
         return ok
 
     def _side_stream(self):
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(self.dev)
         return self._side
 
@@ -241,22 +245,21 @@ class Stage1Engine:
         B, N, Rt = self.cur
         C, D = self.cfg_t.C, self.cfg_t.D
         S, dS = t.S[:Rt], t.dS
-        # the title pass's heads batch (backward_encoder's key): merged into one reduction at its end unless it flushes by bucket
-        pend = []                 # the transform matrices' gradient GEMM rides in the title pass's first grouped launch
+        # the heads batch of the backward that follows (backward_encoder_steps' key): over both parts' sequences, or the title pass's -
+        # merged into one reduction at its end unless it flushes by bucket (under a hook the chained title pass gets one of its own)
         if self.ran_joint:
-            one = after_bucket is None and t.merge_reductions
-            rbh = t.red.setdefault(("heads", "joint", N + B, one), _ReduceBatch(t.dev))
-            if self.cfg_t.T:
-                t._transform_grads(Rt, rbh, pend)
-            T.call("tnr_score_bwd", S, t.cidx, S[N:], t.dscore, dS, dS[N:], B, C, D)
+            key = ("heads", "joint", N + B, after_bucket is None and t.merge_reductions)
+        else:
+            key = ("heads", 0, N, t.merge_reductions and not (self.chain_wgrad and after_bucket is not None))
+        pend = []                 # the transform matrices' gradient GEMM rides in the title pass's first grouped launch
+        if self.cfg_t.T:
+            t._transform_grads(Rt, t.red.setdefault(key, _ReduceBatch(t.dev)), pend)
+        T.call("tnr_score_bwd", S, t.cidx, S[N:], t.dscore, dS, dS[N:], B, C, D)
+        if self.ran_joint:
             # always writes; a layer's weight gradients leave in one grouped launch whose units share one round (Engine._wgrad_flush)
             t.backward_encoder(dS[:Rt], N, after_bucket=after_bucket, pend=pend, parts=self._parts(B, N),
                                side=self._stream_if(self.joint_streams), group_wgrad=self.joint_group_wgrad)
             return
-        one_t = t.merge_reductions and not (self.chain_wgrad and after_bucket is not None)
-        if self.cfg_t.T:
-            t._transform_grads(Rt, t.red.setdefault(("heads", 0, N, one_t), _ReduceBatch(t.dev)), pend)
-        T.call("tnr_score_bwd", S, t.cidx, S[N:], t.dscore, dS, dS[N:], B, C, D)
         if not self.chain_wgrad:
             t.backward_encoder(dS[:N], N, acc=0, pend=pend)
             b.backward_encoder(dS[N:Rt], B, acc=1, after_bucket=after_bucket)
