@@ -493,6 +493,28 @@ int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, float* v, float
                              float lr, float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
                              unsigned stamp, unsigned known_skips, void* stream);
 
+/* Gradient clipping by global norm: torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type = 2) on the gradient the
+ * optimiser consumes, grad_scale * g (the reference has none; an extension, engine.py: Engine.step(max_grad_norm=...)).  State on
+ * the device: part = tnr_grad_sumsq_parts(n) floats per scanned slice, laid one slice behind the other by the caller, and clip =
+ * 2 floats, [0] the coefficient min(1, max_norm / (norm + 1e-6)), [1] norm = grad_scale * sqrt(sum g^2).
+ * tnr_grad_sumsq_scan: ONE pass over the 16-byte-aligned slice g[0 .. n) writes part[0 .. tnr_grad_sumsq_parts(n)), one fp32 sum
+ * of squares per workgroup, and - guard != NULL - raises guard[0] to stamp exactly as tnr_grad_nonfinite_scan does for the same
+ * data (the fp16 build reads its gradient once for both).  Fixed order: per lane four running sums (one per component of its
+ * 16-byte reads, one fma per element), their pairwise sum, the 64 lanes of a wave by butterfly, the four waves in wave order,
+ * one plain store; no float atomics and no arrival counter, the only atomic is the guard's fetch_max from an offending
+ * workgroup.  The grid depends on n alone (tnr_grad_sumsq_parts: host-only, no GPU needed), so the bits are a function of
+ * (n, values).
+ * tnr_grad_clip_commit: one workgroup sums part[0 .. n_part) in double in a fixed order and stores clip[0], clip[1]; a sum of
+ * squares that overflowed fp32 gives norm = inf and coefficient 0, a NaN gives NaN, as torch's fp32 computation does.
+ * tnr_amsgrad_step_clipped = tnr_amsgrad_step_guarded with grad_scale * clip[0] in place of grad_scale (guard == NULL stays
+ * legal: bf16).  All stream-ordered, no host synchronisation; the caller reads clip back whenever it likes. */
+int64_t tnr_grad_sumsq_parts(int64_t n);
+int tnr_grad_sumsq_scan(const float* g, int64_t n, float* part, unsigned* guard, unsigned stamp, void* stream);
+int tnr_grad_clip_commit(const float* part, int64_t n_part, float max_norm, float grad_scale, float* clip, void* stream);
+int tnr_amsgrad_step_clipped(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step,
+                             float lr, float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
+                             unsigned stamp, unsigned known_skips, const float* clip, void* stream);
+
 /* refresh bf16 weight copies after an update: desc = n_desc * 8 int64 on DEVICE:
  * {src fp32 ptr, rows, cols, dst ptr (or 0), dst ld, dstT ptr (or 0), dstT ld, unused}
  * dst[r*ld + c] = bf16(src[r,c]) ; dstT[c*ldT + r] = bf16(src[r,c]), round to nearest even.  Only [0, rows) x [0, cols) of

@@ -14,12 +14,16 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 // knows only with a lag: it passes the factors for step, step - 1, step - 2 and how many skips it has accounted for, the kernel
 // picks by the skips it has not (all factors computed on the host, in double: the same bits as the unguarded launch).
 struct AdamFactors { float lr_c1[3], inv_sqrt_c2[3]; unsigned known_skips; };
-template <bool AMS>
+// CLIP: the gradient is scaled by gscale * clip[0], the coefficient grad_clip_commit_kernel left on the device (global-norm
+// clipping); without it `clip` is never read and the kernel is the unclipped one.
+template <bool AMS, bool CLIP>
 __global__ __launch_bounds__(256) void amsgrad_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v,
                                                       float* __restrict__ vmax, int64_t n, AdamFactors f,
                                                       float b1, float b2, float eps, float gscale,
-                                                      const unsigned* __restrict__ guard, unsigned stamp) {
+                                                      const unsigned* __restrict__ guard, unsigned stamp,
+                                                      const float* __restrict__ clip) {
+    if (CLIP) gscale *= clip[0];
     float lr_c1 = f.lr_c1[0], inv_sqrt_c2 = f.inv_sqrt_c2[0];
     if (guard) {
         if (guard[0] == stamp) return;
@@ -88,6 +92,77 @@ __global__ void grad_nonfinite_count_kernel(unsigned* guard, unsigned stamp) {  
     if (guard[0] == stamp) guard[1] += 1;
 }
 
+// Global-norm clipping: part[blockIdx.x] = sum of g[i]^2 over the 4096-element blocks this workgroup walks -- the memory shape of
+// grad_nonfinite_kernel (16-byte reads, four in flight per lane, the same grid), and with a guard the same answer about inf / nan
+// from the same read.  FIXED ORDER, so the bits depend on (n, values) alone: a lane keeps four running sums, component r of its
+// 16-byte reads feeding sum r by one fma per element (4 per trip of the grid-stride loop), then (s0 + s1) + (s2 + s3), wave_sum,
+// the four waves through LDS in wave order, one plain store.  No float atomics, no arrival counter.
+constexpr int SUMSQ_GRID_CAP = 2048;
+static inline int64_t sumsq_grid(int64_t n) { return std::max<int64_t>(1, std::min<int64_t>((n + 4095) / 4096, SUMSQ_GRID_CAP)); }
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part,
+                                                         unsigned* guard, unsigned stamp) {
+    __shared__ float red[4];
+    const int64_t stride = (int64_t)gridDim.x * 4096;
+    unsigned bad = 0;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t base = (int64_t)blockIdx.x * 4096; base < n; base += stride) {
+        const int64_t i0 = base + threadIdx.x * 4;
+        if (base + 4096 <= n) {
+            u32x4_t b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) b[u] = *(const u32x4_t*)(g + i0 + u * 1024);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    bad |= ((b[u][r] & 0x7F800000u) == 0x7F800000u);
+                    const float x = __uint_as_float(b[u][r]);
+                    acc[r] = __builtin_fmaf(x, x, acc[r]);
+                }
+        } else {
+            for (int u = 0; u < 4; ++u)
+                for (int r = 0; r < 4; ++r) {
+                    const int64_t j = i0 + u * 1024 + r;
+                    if (j < n) {
+                        const float x = g[j];
+                        bad |= ((__float_as_uint(x) & 0x7F800000u) == 0x7F800000u);
+                        acc[r] = __builtin_fmaf(x, x, acc[r]);
+                    }
+                }
+        }
+    }
+    const float s = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    const int any = __syncthreads_or((int)bad);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+        if (guard && any) __hip_atomic_fetch_max(guard, stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// <<<1, 256>>>: the partials of every slice, one behind the other, summed in DOUBLE in a fixed order (thread t takes part[t],
+// part[t + 256], ..., then a halving tree through LDS) -> clip[0] = min(1, max_norm / (norm + 1e-6)), clip[1] = norm =
+// grad_scale * sqrt(sum): torch.nn.utils.clip_grad_norm_ on the gradient the optimiser consumes.  A NaN norm gives a NaN
+// coefficient and an infinite one 0, as torch's clamp does.
+__global__ __launch_bounds__(256) void grad_clip_commit_kernel(const float* __restrict__ part, int64_t n_part, float max_norm,
+                                                               float gscale, float* __restrict__ clip) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n_part; i += 256) s += (double)part[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double norm = (double)gscale * sqrt(red[0]);
+        const double c = (double)max_norm / (norm + 1e-6);
+        clip[0] = (float)(c > 1.0 ? 1.0 : c);
+        clip[1] = (float)norm;
+    }
+}
+
 }  // namespace
 
 extern "C" int tnr_amsgrad_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
@@ -119,9 +194,9 @@ extern "C" int tnr_grad_nonfinite(const float* g, int64_t n, unsigned* guard, un
     return TNR_OK;
 }
 
-extern "C" int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
-                                        float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
-                                        unsigned stamp, unsigned known_skips, void* stream) {
+static int amsgrad_launch(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr, float beta1,
+                          float beta2, float eps, float grad_scale, const unsigned* guard, unsigned stamp, unsigned known_skips,
+                          const float* clip, void* stream) {
     TNR_CHECK_ARG(p && g && m && v && n >= 1 && step >= 1, "tnr_amsgrad_step: bad argument");     // vmax NULL = plain Adam
     TNR_CHECK_ARG(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
                       ((uintptr_t)v % 16) == 0 && ((uintptr_t)vmax % 16) == 0, "tnr_amsgrad_step: 16-byte alignment");
@@ -134,12 +209,47 @@ extern "C" int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, floa
     }
     f.known_skips = known_skips;
     int64_t nthr = (n + 3) / 4;
-    if (vmax)
-        hipLaunchKernelGGL(amsgrad_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m,
-                           v, vmax, n, f, beta1, beta2, eps, grad_scale, guard, stamp);
-    else      // plain Adam (Post-train_KD.ipynb cell 18: optim.Adam without amsgrad)
-        hipLaunchKernelGGL(amsgrad_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m,
-                           v, vmax, n, f, beta1, beta2, eps, grad_scale, guard, stamp);
+    const dim3 grid((unsigned)((nthr + 255) / 256));
+#define TNR_AMSGRAD_LAUNCH(AMS, CLIP)                                                                                        \
+    hipLaunchKernelGGL((amsgrad_kernel<AMS, CLIP>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, f, beta1, \
+                       beta2, eps, grad_scale, guard, stamp, clip)
+    if (vmax) {
+        if (clip) TNR_AMSGRAD_LAUNCH(true, true);
+        else TNR_AMSGRAD_LAUNCH(true, false);
+    } else {  // plain Adam (Post-train_KD.ipynb cell 18: optim.Adam without amsgrad)
+        if (clip) TNR_AMSGRAD_LAUNCH(false, true);
+        else TNR_AMSGRAD_LAUNCH(false, false);
+    }
+#undef TNR_AMSGRAD_LAUNCH
     TNR_CHECK_LAUNCH("tnr_amsgrad_step");
+    return TNR_OK;
+}
+
+extern "C" int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
+                                        float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
+                                        unsigned stamp, unsigned known_skips, void* stream) {
+    return amsgrad_launch(p, g, m, v, vmax, n, step, lr, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, nullptr, stream);
+}
+
+extern "C" int tnr_amsgrad_step_clipped(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
+                                        float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
+                                        unsigned stamp, unsigned known_skips, const float* clip, void* stream) {
+    TNR_CHECK_ARG(clip && ((uintptr_t)clip % 4) == 0, "tnr_amsgrad_step_clipped: clip must point at the two floats of tnr_grad_clip_commit");
+    return amsgrad_launch(p, g, m, v, vmax, n, step, lr, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, clip, stream);
+}
+
+extern "C" int64_t tnr_grad_sumsq_parts(int64_t n) { return sumsq_grid(n); }
+
+extern "C" int tnr_grad_sumsq_scan(const float* g, int64_t n, float* part, unsigned* guard, unsigned stamp, void* stream) {
+    TNR_CHECK_ARG(g && part && n >= 1 && ((uintptr_t)g % 16) == 0 && (!guard || stamp >= 1), "tnr_grad_sumsq_scan: bad argument");
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)sumsq_grid(n)), dim3(256), 0, (hipStream_t)stream, g, n, part, guard, stamp);
+    TNR_CHECK_LAUNCH("tnr_grad_sumsq_scan");
+    return TNR_OK;
+}
+
+extern "C" int tnr_grad_clip_commit(const float* part, int64_t n_part, float max_norm, float grad_scale, float* clip, void* stream) {
+    TNR_CHECK_ARG(part && clip && n_part >= 1 && max_norm > 0.f, "tnr_grad_clip_commit: bad argument");
+    hipLaunchKernelGGL(grad_clip_commit_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, n_part, max_norm, grad_scale, clip);
+    TNR_CHECK_LAUNCH("tnr_grad_clip_commit");
     return TNR_OK;
 }

@@ -322,6 +322,10 @@ class Engine:
             for k in ("shapes", "slot", "n_train", "n_frozen", "flat", "flat_g", "adam_m", "adam_v", "adam_vmax", "params",
                       "grads", "lo", "sh", "sh_a1", "sh_a1T", "b_a1", "desc_all", "desc_train"):
                 setattr(self, k, getattr(share, k))
+        # global-norm gradient clipping (step(max_grad_norm=...)): buffers come with the first clipped step and belong to the engine
+        # that owns flat_g; never requested, nothing is allocated
+        self._clip_owner = self if share is None else share._clip_owner
+        self._clip_state = None
         self.max_batch = max_batch
         self.extra_rows, self.extra_seqs = int(extra_rows), int(extra_seqs)
         self.drop = None             # set_dropout(): train-mode dropout of the stage-0 / stage-1 notebooks
@@ -1491,13 +1495,51 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ optimiser
-    def step(self, lr, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, lr_bert=None, amsgrad=True, lr_news_head=None, sync=None):
+    def _clip_buffers(self):
+        """State of global-norm clipping, made on first use by the engine that owns flat_g (engines built with share= use it):
+        the scanned slices (bucket_ranges()) with the offset of each one's partial sums, the partial buffer sized through
+        tnr_grad_sumsq_parts, the two floats (coefficient, norm) on the device and a pinned ring for their read-back."""
+        own = self._clip_owner
+        if own._clip_state is None:
+            slices, off = [], 0
+            for s_, e_ in own.bucket_ranges():
+                slices.append((s_, e_, off))
+                off += T.query("tnr_grad_sumsq_parts", e_ - s_)
+            own._clip_state = SimpleNamespace(slices=slices, n_part=off, part=torch.zeros(off, dtype=torch.float32, device=own.dev),
+                                              clip=torch.zeros(2, dtype=torch.float32, device=own.dev),
+                                              ring=torch.zeros(8, 2, dtype=torch.float32).pin_memory(), count=0, last=None)
+        return own._clip_state
+
+    def grad_norm(self):
+        """(total_norm, coef) of the last clipped step: the norm of grad_scale * (the reduced gradient) and the coefficient the
+        update multiplied it by.  Read back asynchronously: step() queued a 8-byte copy into pinned memory and an event behind its
+        commit kernel, and this waits for that event only - neither it nor step() drains the device.  None before the first
+        clipped step.  fp16: the values of a step the overflow guard skipped are meaningless."""
+        cs = self._clip_owner._clip_state
+        if cs is None or cs.last is None:
+            return None
+        host, ev = cs.last
+        ev.synchronize()
+        return float(host[1]), float(host[0])
+
+    def step(self, lr, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, lr_bert=None, amsgrad=True, lr_news_head=None, sync=None,
+             max_grad_norm=None):
         """torch.optim.Adam(amsgrad=True).step() (run.py:134,195) + refresh of the 16-bit weight copies.
         lr_bert / lr_news_head: learning rates of the encoder layers / of the news encoder's pooling + dense when they
         differ (PLM-NR/run.py:104-106: {'params': pretrained, 'lr': pretrain_lr}, {'params': rest, 'lr': lr}; the notebooks
         use 1e-6 for bert_model and 1e-5 for the rest).  amsgrad=False: plain Adam (Post-train_KD.ipynb cell 18).
         sync: a dist.GradSync with all-reduces in flight -- the update then runs bucket by bucket in completion order, each
-        slice behind its own collective only (elementwise optimiser: the same bits as one launch over everything)."""
+        slice behind its own collective only (elementwise optimiser: the same bits as one launch over everything).
+        max_grad_norm > 0: torch.nn.utils.clip_grad_norm_(all trainable parameters, max_grad_norm) on grad_scale * flat_g, i.e.
+        AFTER the data-parallel reduction (a clip_grad_norm_ between backward() and step() would see the un-reduced gradient) and
+        on the device: ONE norm over everything trainable, whatever the learning-rate ranges.  The gradient is then ALWAYS scanned
+        slice by slice over bucket_ranges() in that order (tnr_grad_sumsq_scan, which under fp16 is the overflow guard's scan as
+        well; with a pending sync each bucket behind its own wait_bucket), so the coefficient's bits do not depend on whether
+        the step ran data-parallel; then tnr_grad_nonfinite_commit (fp16), tnr_grad_clip_commit and the update of every rate range
+        through tnr_amsgrad_step_clipped.  A global norm needs the whole gradient first, so under bf16 this REPLACES the
+        bucket-by-bucket update: the update waits for the last bucket, as fp16's always does.  grad_norm() reads the result back.
+        None or <= 0: off - the calls, kernels, bits and buffers of a step without it."""
+        clip_on = max_grad_norm is not None and max_grad_norm > 0
         sc = self.scaler
         guard, stamp = None, 0
         if sc.enabled:
@@ -1521,12 +1563,38 @@ class Engine:
             if hi_ > lo_:
                 args = (self.flat[True][lo_:hi_], self.flat_g[lo_:hi_], self.adam_m[lo_:hi_], self.adam_v[lo_:hi_],
                         self.adam_vmax[lo_:hi_] if amsgrad else None, hi_ - lo_, self.step_count, rate, beta1, beta2, eps, grad_scale)
-                if guard is None:
+                if clip_on:
+                    T.call("tnr_amsgrad_step_clipped", *args, guard, stamp, sc.skipped if guard is not None else 0, cs.clip)
+                elif guard is None:
                     T.call("tnr_amsgrad_step", *args)
                 else:
                     T.call("tnr_amsgrad_step_guarded", *args, guard, stamp, sc.skipped)
 
-        if guard is not None:
+        if clip_on:
+            cs = self._clip_buffers()
+            bucketed = sync is not None and sync.pending
+            if bucketed:
+                assert [tuple(r) for r in sync.ranges] == [(s_, e_) for s_, e_, _ in cs.slices], "sync buckets are not bucket_ranges()"
+            elif sync is not None:
+                sync.wait()
+            for b, (s_, e_, off) in enumerate(cs.slices):
+                if bucketed:
+                    sync.wait_bucket(b)
+                T.call("tnr_grad_sumsq_scan", self.flat_g[s_:e_], e_ - s_, cs.part[off:], guard, stamp)
+            if guard is not None:
+                T.call("tnr_grad_nonfinite_commit", guard, stamp)
+            T.call("tnr_grad_clip_commit", cs.part, cs.n_part, float(max_grad_norm), grad_scale, cs.clip)
+            for lo_, hi_, rate in ranges:
+                launch(lo_, hi_, rate)
+            if guard is not None:
+                sc.record(used)
+            host = cs.ring[cs.count % 8]
+            cs.count += 1
+            host.copy_(cs.clip, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            cs.last = (host, ev)
+        elif guard is not None:
             # the WHOLE (reduced) gradient decides before any slice is updated - identically on every rank, since inf / nan
             # survive the all-reduce.  Under data parallelism each bucket is scanned as soon as ITS all-reduce has landed (the
             # scans hide under the collectives still in flight; what lies between buckets are alignment gaps, zero gradients); only

@@ -33,6 +33,7 @@ def _flag_table():
           ("teacher_ckpts", str, [], dict(nargs="+")), ("teacher_emb_paths", str, [], dict(nargs="+")),
           # additions (defaults keep the reference behaviour)
           ("train_embeddings", _B, False, dict(help="also fine-tune bert.embeddings.* (word / position / token-type tables and the embedding LayerNorm) at the encoder's learning rate; the reference freezes them (run.py:101-112); needs --bert_trainable_layer")),
+          ("max_grad_norm", float, 0.0, dict(help="clip the gradient by its global L2 norm, torch.nn.utils.clip_grad_norm_ semantics (one norm over everything trainable, coef = min(1, max_norm / (norm + 1e-6))), done on the device after the gradient all-reduce; 0 = off (the reference does not clip)")),
           ("resident_tables", _B, True, dict(help="keep news_combined / teacher tables in HBM and ship indices only")),
           ("cache_frozen_layers", _B, True, dict(help="resident mode: compute the frozen lower encoder layers once per news instead of every step (identical results)")),
           ("dedup_news", _B, True, dict(help="encode each distinct news of a batch once (resident mode; identical results)")),

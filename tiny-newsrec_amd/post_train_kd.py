@@ -61,6 +61,9 @@ def parse_args(argv=None):
                    "continued from a checkpoint should pass a different seed (as a fixed torch seed would replay the notebook's masks)")
     p.add_argument("--enable_hvd", type=b, default=True, help="data-parallel when launched by torch.distributed.run")
     p.add_argument("--dtype", default="fp16", choices=["bf16", "fp16"])
+    p.add_argument("--max_grad_norm", type=float, default=0.0,
+                   help="clip the gradient by its global L2 norm, torch.nn.utils.clip_grad_norm_ semantics (one norm over the title + body "
+                        "gradient of everything trainable), on the device after the gradient all-reduce; 0 = off (the notebooks do not clip)")
     p.add_argument("--hidden_dropout_prob", type=float, default=None,
                    help="train-mode dropout (the notebooks call .train(): cell 19:6 / cell 16:6); default = the value in --config_name "
                         "(tnlrv3/config/*.json:4, 0.1), 0 turns it off")
@@ -229,7 +232,8 @@ def train(args):
             sums[3] += losses[2]
             sums[4] += utils.acc(label, score)
             eng.backward(after_bucket=sync.launch if sync else None)
-            eng.step(args.lr, grad_scale=sync.scale if sync else 1.0, lr_bert=args.pretrain_lr, amsgrad=False, sync=sync)
+            clip_kw = {"max_grad_norm": args.max_grad_norm} if args.max_grad_norm > 0 else {}
+            eng.step(args.lr, grad_scale=sync.scale if sync else 1.0, lr_bert=args.pretrain_lr, amsgrad=False, sync=sync, **clip_kw)
             if args.stage == 0 and rank == 0 and cnt % args.save_steps == 0:          # cell 16: DP_12_layer_{cnt}.pt
                 os.makedirs(args.save_dir, exist_ok=True)
                 torch.save({"model_state_dict": _ckpt_state(eng, 0)},
@@ -237,9 +241,11 @@ def train(args):
             if cnt % args.log_steps == 0:
                 s = (sums / cnt).tolist()
                 sc = eng.title.scaler
-                logging.info("[%d] ed: %d, loss: %.5f, t_loss: %.5f, d_loss: %.5f, e_loss: %.5f, acc: %.5f, %.1f pairs/s%s" % (
+                gn = eng.grad_norm() if clip_kw else None
+                logging.info("[%d] ed: %d, loss: %.5f, t_loss: %.5f, d_loss: %.5f, e_loss: %.5f, acc: %.5f, %.1f pairs/s%s%s" % (
                     rank, cnt * B, s[0], s[1], s[2], s[3], s[4], size * cnt * B / max(time.time() - t0, 1e-9),
-                    ", loss scale %g, %d steps skipped (fp16 overflow)" % (eng.title.gscale, sc.skipped) if sc.enabled and sc.skipped else ""))
+                    ", loss scale %g, %d steps skipped (fp16 overflow)" % (eng.title.gscale, sc.skipped) if sc.enabled and sc.skipped else "",
+                    ", grad norm {:g} (clip x{:.3g})".format(*gn) if gn is not None else ""))
         if eng.title.scaler.enabled:
             eng.title.scaler.drain(eng.title)
         if rank == 0:

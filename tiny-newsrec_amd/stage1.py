@@ -338,3 +338,7 @@ class Stage1Engine:
     def step(self, lr, grad_scale=1.0, lr_bert=None, amsgrad=False, **kw):
         """Post-train_KD.ipynb cell 18: optim.Adam([{bert_model, 1e-6}, {rest, 1e-5}]) (plain Adam by default here)."""
         self.title.step(lr, grad_scale, lr_bert=lr_bert, amsgrad=amsgrad, **kw)
+
+    def grad_norm(self):
+        """Engine.grad_norm of the last step(max_grad_norm=...): one norm over the title + body gradient (one flat buffer)."""
+        return self.title.grad_norm()

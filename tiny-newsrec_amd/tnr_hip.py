@@ -164,6 +164,10 @@ _SIG = {
     "tnr_grad_nonfinite": [_P, _L, _P, _c.c_uint, _P],
     "tnr_grad_nonfinite_scan": [_P, _L, _P, _c.c_uint, _P],
     "tnr_grad_nonfinite_commit": [_P, _c.c_uint, _P],
+    "tnr_grad_sumsq_parts": [_L],
+    "tnr_grad_sumsq_scan": [_P, _L, _P, _P, _c.c_uint, _P],
+    "tnr_grad_clip_commit": [_P, _L, _F, _F, _P, _P],
+    "tnr_amsgrad_step_clipped": [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P, _c.c_uint, _c.c_uint, _P, _P],
     "tnr_refresh_shadows": [_P, _I, _L, _P, _P],
     "tnr_cast_f32_to_bf16": [_P, _P, _L, _P],
     "tnr_cast_bf16_to_f32": [_P, _P, _L, _P],
@@ -186,7 +190,7 @@ TYPED += ["tnr_gemm_nt_do", "tnr_ln_bwd_do", "tnr_gemm_nt_do_split", "tnr_ln_bwd
 for _n in TYPED:
     _SIG[_n + "_f16"] = _SIG[_n]
 _RET = {"tnr_attpool_long_ws_elems": _L, "tnr_attpool_long_ws_elems_f16": _L, "tnr_gemm_tn_ws_elems": _L, "tnr_gemm_tn_ws_elems_f16": _L, "tnr_gemm_colsum_rows_f16": _L, "tnr_gemm_colsum_rows": _L, "tnr_ln_bwd_part_elems": _L, "tnr_ln_bwd_blocks": _L, "tnr_embed_ln_bwd_part_elems": _L, "tnr_embed_ln_bwd_blocks": _L, "tnr_colsum_part_elems": _L,
-        "tnr_user_bwd_part_stride": _L}
+        "tnr_user_bwd_part_stride": _L, "tnr_grad_sumsq_parts": _L}
 EXPORTS = sorted(_SIG) + ["tnr_last_error"]
 
 _lib = None
