@@ -515,6 +515,30 @@ int tnr_amsgrad_step_clipped(float* p, const float* g, float* m, float* v, float
                              float lr, float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
                              unsigned stamp, unsigned known_skips, const float* clip, void* stream);
 
+/* Decoupled weight decay and a learning-rate schedule in the fused update: torch.optim.AdamW(amsgrad = vmax != NULL) with
+ * lr_scheduler.LambdaLR semantics (the reference has neither; an extension, engine.py: Engine.step(weight_decay=, warmup_steps=,
+ * lr_decay_steps=)).  tnr_adamw_step = tnr_amsgrad_step_guarded / _clipped (guard and clip both nullable) with
+ *   - THREE learning rates: lr_k is the (scheduled) rate of the update if t_k = max(step - k, 1) updates have been taken, this one
+ *     included, k = 0, 1, 2 - the candidates the bias corrections already have, picked on the device by guard[1] - known_skips
+ *     (k >= 2 -> lr2), so a schedule follows the updates TAKEN and a skipped step advances neither Adam's count nor the schedule.
+ *     The caller computes them (engine.lr_schedule: linear warmup from 0, then linear decay or constant); lr0 == lr1 == lr2 and
+ *     weight_decay == 0 give the bits of tnr_amsgrad_step / _guarded / _clipped.
+ *   - weight_decay >= 0, decoupled, in torch's order: for an element whose bit is set in decay_bits, p <- p * (1 - lr_k *
+ *     weight_decay) first, then the Adam / AMSGrad update on the UNDECAYED gradient grad_scale * g (x clip[0] when clip is given:
+ *     the decay does not see the clip coefficient).  lr_k * weight_decay is formed on the host in double.  A launch stamped
+ *     guard[0] decays nothing.
+ *   - decay_bits: one bit per element of the WHOLE flat buffer the slice p[0 .. n) was cut from, uint32 words on the device,
+ *     element e = bit (e & 31) of word e >> 5; `first` = the slice's element offset in that buffer, a multiple of 4 (as the
+ *     16-byte alignment of p implies when the buffer is 16-byte aligned), so a thread's four bits never straddle a word.  The map
+ *     must hold at least (first + n + 31) / 32 words.  NULL is legal iff weight_decay == 0; then the map and `first` are not read
+ *     and the kernel is the one without decay.
+ * Errors (no launch): first % 4 != 0 or < 0, weight_decay > 0 with a NULL map, weight_decay < 0, and everything
+ * tnr_amsgrad_step_guarded refuses. */
+int tnr_adamw_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr0, float lr1,
+                   float lr2, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                   const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp, unsigned known_skips,
+                   const float* clip, void* stream);
+
 /* refresh bf16 weight copies after an update: desc = n_desc * 8 int64 on DEVICE:
  * {src fp32 ptr, rows, cols, dst ptr (or 0), dst ld, dstT ptr (or 0), dstT ld, unused}
  * dst[r*ld + c] = bf16(src[r,c]) ; dstT[c*ldT + r] = bf16(src[r,c]), round to nearest even.  Only [0, rows) x [0, cols) of

@@ -13,26 +13,40 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 // the skipped step of dynamic loss scaling.  Adam's bias corrections depend on the number of steps actually TAKEN, which the host
 // knows only with a lag: it passes the factors for step, step - 1, step - 2 and how many skips it has accounted for, the kernel
 // picks by the skips it has not (all factors computed on the host, in double: the same bits as the unguarded launch).
+// The learning rate may differ between the three candidates (a warmup / decay schedule follows the steps TAKEN, like the bias
+// corrections): lr_c1[k] = lr_k / c1(t_k), and for the decay lr_wd[k] = lr_k * weight_decay.  lr_wd travels in a struct of its own
+// BEHIND every other argument: inside AdamFactors it would move the arguments after it, and the instantiations without decay
+// would no longer be, instruction for instruction, the kernels they were.
 struct AdamFactors { float lr_c1[3], inv_sqrt_c2[3]; unsigned known_skips; };
+struct AdamDecay { float lr_wd[3]; };
 // CLIP: the gradient is scaled by gscale * clip[0], the coefficient grad_clip_commit_kernel left on the device (global-norm
 // clipping); without it `clip` is never read and the kernel is the unclipped one.
-template <bool AMS, bool CLIP>
+// WD: decoupled weight decay in torch.optim.AdamW's order - p *= 1 - lr_k wd first, then the update on the undecayed gradient
+// (the decay sees neither grad_scale nor the clip coefficient) - for the elements whose bit is set in `wbits`: one bit per
+// element of the WHOLE flat buffer, bit (e & 31) of word e >> 5, this launch's slice starting at element `first` of it.  first and
+// a thread's offset are multiples of 4, so its four bits are one nibble of one word.  Without WD neither wbits, first nor lr_wd is
+// read and the kernel is the one without decay.  A launch stamped guard[0] decays nothing.
+template <bool AMS, bool CLIP, bool WD>
 __global__ __launch_bounds__(256) void amsgrad_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v,
                                                       float* __restrict__ vmax, int64_t n, AdamFactors f,
                                                       float b1, float b2, float eps, float gscale,
                                                       const unsigned* __restrict__ guard, unsigned stamp,
-                                                      const float* __restrict__ clip) {
+                                                      const float* __restrict__ clip,
+                                                      const unsigned* __restrict__ wbits, int64_t first, AdamDecay d) {
     if (CLIP) gscale *= clip[0];
-    float lr_c1 = f.lr_c1[0], inv_sqrt_c2 = f.inv_sqrt_c2[0];
+    float lr_c1 = f.lr_c1[0], inv_sqrt_c2 = f.inv_sqrt_c2[0], keep = 1.f;
+    if (WD) keep = 1.f - d.lr_wd[0];
     if (guard) {
         if (guard[0] == stamp) return;
         const unsigned k = guard[1] - f.known_skips;
-        if (k == 1) { lr_c1 = f.lr_c1[1]; inv_sqrt_c2 = f.inv_sqrt_c2[1]; }
-        else if (k >= 2) { lr_c1 = f.lr_c1[2]; inv_sqrt_c2 = f.inv_sqrt_c2[2]; }
+        if (k == 1) { lr_c1 = f.lr_c1[1]; inv_sqrt_c2 = f.inv_sqrt_c2[1]; if (WD) keep = 1.f - d.lr_wd[1]; }
+        else if (k >= 2) { lr_c1 = f.lr_c1[2]; inv_sqrt_c2 = f.inv_sqrt_c2[2]; if (WD) keep = 1.f - d.lr_wd[2]; }
     }
     int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
+    unsigned nib = 0;                       // bit r: element i + r decays (i < n, so the word lies inside the map)
+    if (WD) nib = wbits[(first + i) >> 5] >> ((unsigned)(first + i) & 31u);
     if (i + 4 <= n) {
         f32x4 gv = *(const f32x4*)(g + i) * gscale;
         f32x4 mv = *(const f32x4*)(m + i) * b1 + (1.f - b1) * gv;
@@ -43,6 +57,7 @@ __global__ __launch_bounds__(256) void amsgrad_kernel(float* __restrict__ p, con
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (AMS) vm[r] = fmaxf(vm[r], vv[r]);
+            if (WD) pv[r] = (nib >> r) & 1u ? pv[r] * keep : pv[r];
             pv[r] -= lr_c1 * (mv[r] / (sqrtf(vm[r]) * inv_sqrt_c2 + eps));
         }
         *(f32x4*)(m + i) = mv;
@@ -50,14 +65,16 @@ __global__ __launch_bounds__(256) void amsgrad_kernel(float* __restrict__ p, con
         if (AMS) *(f32x4*)(vmax + i) = vm;
         *(f32x4*)(p + i) = pv;
     } else {
-        for (; i < n; ++i) {
+        for (; i < n; ++i, nib >>= 1) {
             float gv = g[i] * gscale;
             float mv = m[i] * b1 + (1.f - b1) * gv;
             float vv = v[i] * b2 + (1.f - b2) * gv * gv;
             float vm = AMS ? fmaxf(vmax[i], vv) : vv;
             m[i] = mv; v[i] = vv;
             if (AMS) vmax[i] = vm;
-            p[i] -= lr_c1 * (mv / (sqrtf(vm) * inv_sqrt_c2 + eps));
+            float pv = p[i];
+            if (WD) pv = nib & 1u ? pv * keep : pv;
+            p[i] = pv - lr_c1 * (mv / (sqrtf(vm) * inv_sqrt_c2 + eps));
         }
     }
 }
@@ -194,32 +211,40 @@ extern "C" int tnr_grad_nonfinite(const float* g, int64_t n, unsigned* guard, un
     return TNR_OK;
 }
 
-static int amsgrad_launch(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr, float beta1,
-                          float beta2, float eps, float grad_scale, const unsigned* guard, unsigned stamp, unsigned known_skips,
-                          const float* clip, void* stream) {
+// lr[k]: the learning rate of candidate k (all three equal without a schedule); weight_decay > 0 needs the decay map.
+static int amsgrad_launch(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, const float* lr,
+                          float beta1, float beta2, float eps, float grad_scale, const unsigned* guard, unsigned stamp,
+                          unsigned known_skips, const float* clip, float weight_decay, const unsigned* decay_bits, int64_t first,
+                          void* stream) {
     TNR_CHECK_ARG(p && g && m && v && n >= 1 && step >= 1, "tnr_amsgrad_step: bad argument");     // vmax NULL = plain Adam
     TNR_CHECK_ARG(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
                       ((uintptr_t)v % 16) == 0 && ((uintptr_t)vmax % 16) == 0, "tnr_amsgrad_step: 16-byte alignment");
+    const bool wd = weight_decay != 0.f;
     AdamFactors f;
+    AdamDecay d;
     for (int k = 0; k < 3; ++k) {
         const int t = step - k >= 1 ? step - k : 1;
         const double c1 = 1.0 - pow((double)beta1, t), c2 = 1.0 - pow((double)beta2, t);
-        f.lr_c1[k] = (float)((double)lr / c1);
+        f.lr_c1[k] = (float)((double)lr[k] / c1);
         f.inv_sqrt_c2[k] = (float)(1.0 / sqrt(c2));
+        d.lr_wd[k] = (float)((double)lr[k] * (double)weight_decay);
     }
     f.known_skips = known_skips;
     int64_t nthr = (n + 3) / 4;
     const dim3 grid((unsigned)((nthr + 255) / 256));
-#define TNR_AMSGRAD_LAUNCH(AMS, CLIP)                                                                                        \
-    hipLaunchKernelGGL((amsgrad_kernel<AMS, CLIP>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, f, beta1, \
-                       beta2, eps, grad_scale, guard, stamp, clip)
+#define TNR_AMSGRAD_LAUNCH(AMS, CLIP, WD)                                                                                        \
+    hipLaunchKernelGGL((amsgrad_kernel<AMS, CLIP, WD>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, f, beta1, \
+                       beta2, eps, grad_scale, guard, stamp, clip, decay_bits, first, d)
+#define TNR_AMSGRAD_LAUNCH_WD(AMS, CLIP)                                                                                         \
+    do { if (wd) TNR_AMSGRAD_LAUNCH(AMS, CLIP, true); else TNR_AMSGRAD_LAUNCH(AMS, CLIP, false); } while (0)
     if (vmax) {
-        if (clip) TNR_AMSGRAD_LAUNCH(true, true);
-        else TNR_AMSGRAD_LAUNCH(true, false);
+        if (clip) TNR_AMSGRAD_LAUNCH_WD(true, true);
+        else TNR_AMSGRAD_LAUNCH_WD(true, false);
     } else {  // plain Adam (Post-train_KD.ipynb cell 18: optim.Adam without amsgrad)
-        if (clip) TNR_AMSGRAD_LAUNCH(false, true);
-        else TNR_AMSGRAD_LAUNCH(false, false);
+        if (clip) TNR_AMSGRAD_LAUNCH_WD(false, true);
+        else TNR_AMSGRAD_LAUNCH_WD(false, false);
     }
+#undef TNR_AMSGRAD_LAUNCH_WD
 #undef TNR_AMSGRAD_LAUNCH
     TNR_CHECK_LAUNCH("tnr_amsgrad_step");
     return TNR_OK;
@@ -228,14 +253,31 @@ static int amsgrad_launch(float* p, const float* g, float* m, float* v, float* v
 extern "C" int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
                                         float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
                                         unsigned stamp, unsigned known_skips, void* stream) {
-    return amsgrad_launch(p, g, m, v, vmax, n, step, lr, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, nullptr, stream);
+    const float lrs[3] = {lr, lr, lr};
+    return amsgrad_launch(p, g, m, v, vmax, n, step, lrs, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, nullptr, 0.f,
+                          nullptr, 0, stream);
 }
 
 extern "C" int tnr_amsgrad_step_clipped(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
                                         float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
                                         unsigned stamp, unsigned known_skips, const float* clip, void* stream) {
     TNR_CHECK_ARG(clip && ((uintptr_t)clip % 4) == 0, "tnr_amsgrad_step_clipped: clip must point at the two floats of tnr_grad_clip_commit");
-    return amsgrad_launch(p, g, m, v, vmax, n, step, lr, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, clip, stream);
+    const float lrs[3] = {lr, lr, lr};
+    return amsgrad_launch(p, g, m, v, vmax, n, step, lrs, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, clip, 0.f,
+                          nullptr, 0, stream);
+}
+
+extern "C" int tnr_adamw_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr0, float lr1,
+                              float lr2, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                              const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp,
+                              unsigned known_skips, const float* clip, void* stream) {
+    TNR_CHECK_ARG(weight_decay >= 0.f && (weight_decay == 0.f || decay_bits) && ((uintptr_t)decay_bits % 4) == 0,
+                  "tnr_adamw_step: weight_decay > 0 needs the decay map (and none below 0)");
+    TNR_CHECK_ARG(first >= 0 && first % 4 == 0, "tnr_adamw_step: first must be a multiple of 4 (a thread's four bits in one word)");
+    TNR_CHECK_ARG(((uintptr_t)clip % 4) == 0, "tnr_adamw_step: clip must point at the two floats of tnr_grad_clip_commit");
+    const float lrs[3] = {lr0, lr1, lr2};
+    return amsgrad_launch(p, g, m, v, vmax, n, step, lrs, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, clip,
+                          weight_decay, decay_bits, first, stream);
 }
 
 extern "C" int64_t tnr_grad_sumsq_parts(int64_t n) { return sumsq_grid(n); }

@@ -15,6 +15,7 @@ import math
 import struct
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 import tnr_hip as T
@@ -226,6 +227,34 @@ class _ReduceBatch:
                 T.call("tnr_reduce_multi", t[0], t[1])
 
 
+def lr_schedule(u, warmup_steps=0, lr_decay_steps=0):
+    """Multiplier of every learning rate at an update that `u` updates precede (step(warmup_steps=W, lr_decay_steps=T)):
+    u / W while u < W (the first update has rate 0), then max(0, (T - u) / max(1, T - W)) if T > 0 and 1 if T == 0 -
+    transformers' get_linear_schedule_with_warmup / get_constant_schedule_with_warmup as LambdaLR applies them.  W = T = 0: 1."""
+    u, W, T_ = int(u), int(warmup_steps or 0), int(lr_decay_steps or 0)
+    if u < W:
+        return u / W
+    if T_ > 0:
+        return max(0.0, (T_ - u) / max(1, T_ - W))
+    return 1.0
+
+
+def decays(name, shape):
+    """The decay set of step(weight_decay=...): 2-D `.weight`s outside LayerNorm (Linear and embedding matrices); biases, every
+    LayerNorm parameter and pad_doc are exempt."""
+    return name.endswith(".weight") and len(shape) == 2 and "LayerNorm" not in name
+
+
+def decay_words(slot, n_train):
+    """One bit per element of the flat trainable buffer (element e = bit e & 31 of word e >> 5, uint32), set for the elements of
+    the parameters that decay; alignment gaps and reserved rows stay clear.  A pure host function of the slot table."""
+    bits = np.zeros(_rup(n_train, 32), dtype=bool)
+    for name, (tr, o, n, shp) in slot.items():
+        if tr and decays(name, shp):
+            bits[o:o + n] = True
+    return np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).copy()
+
+
 LOSS_SCALE = 1024.0     # static scale of the 16-bit backward in fp16 mode (gradients of ~1e-6 would underflow); it enters at
                         # the pooling backward and leaves in the kernels that write parameter gradients (weight-gradient slab
                         # reduce, bias / LayerNorm partial reductions), so flat_g always holds the true gradients
@@ -326,6 +355,8 @@ class Engine:
         # that owns flat_g; never requested, nothing is allocated
         self._clip_owner = self if share is None else share._clip_owner
         self._clip_state = None
+        self._decay_map = None       # step(weight_decay > 0): the owner's decay bits on the device, made on first use
+        self.lr_scale = None         # the host's multiplier of the last step's learning rates while a schedule is on, else None
         self.max_batch = max_batch
         self.extra_rows, self.extra_seqs = int(extra_rows), int(extra_seqs)
         self.drop = None             # set_dropout(): train-mode dropout of the stage-0 / stage-1 notebooks
@@ -1522,8 +1553,17 @@ class Engine:
         ev.synchronize()
         return float(host[1]), float(host[0])
 
+    def _decay_bits(self):
+        """The decay map (decay_words of the slot table) on the device, made on first use by the engine that owns flat_g; engines
+        built with share= use the owner's."""
+        own = self._clip_owner
+        if own._decay_map is None:
+            words = decay_words(own.slot, own.n_train)
+            own._decay_map = torch.from_numpy(words.view(np.int32)).to(own.dev)
+        return own._decay_map
+
     def step(self, lr, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, lr_bert=None, amsgrad=True, lr_news_head=None, sync=None,
-             max_grad_norm=None):
+             max_grad_norm=None, weight_decay=0.0, warmup_steps=0, lr_decay_steps=0):
         """torch.optim.Adam(amsgrad=True).step() (run.py:134,195) + refresh of the 16-bit weight copies.
         lr_bert / lr_news_head: learning rates of the encoder layers / of the news encoder's pooling + dense when they
         differ (PLM-NR/run.py:104-106: {'params': pretrained, 'lr': pretrain_lr}, {'params': rest, 'lr': lr}; the notebooks
@@ -1538,8 +1578,23 @@ class Engine:
         the step ran data-parallel; then tnr_grad_nonfinite_commit (fp16), tnr_grad_clip_commit and the update of every rate range
         through tnr_amsgrad_step_clipped.  A global norm needs the whole gradient first, so under bf16 this REPLACES the
         bucket-by-bucket update: the update waits for the last bucket, as fp16's always does.  grad_norm() reads the result back.
-        None or <= 0: off - the calls, kernels, bits and buffers of a step without it."""
+        None or <= 0: off - the calls, kernels, bits and buffers of a step without it.
+        weight_decay > 0: torch.optim.AdamW's decoupled decay - p *= 1 - lr_k weight_decay, then the update on the undecayed
+        (clipped) gradient - for the 2-D `.weight`s outside LayerNorm (decays(): biases, LayerNorm parameters, pad_doc and
+        alignment gaps are exempt; with train_embeddings the three embedding tables decay), ONE value for every rate range; the
+        decay set lives on the device as one bit per element of the flat buffer (decay_words, made once by the owner of flat_g).
+        warmup_steps = W, lr_decay_steps = T: every rate is multiplied by lr_schedule(u, W, T), u = the number of updates TAKEN
+        before this one, from the step_count the bias corrections use: under fp16 the kernel gets the rates of u, u - 1, u - 2
+        beside the three bias corrections and picks by the skips the host has not accounted for, so a skipped step advances
+        neither Adam's count nor the schedule and decays nothing.  The position is optimiser state (not checkpointed, like m, v,
+        vmax).  With any of the three on, every range / bucket launch goes through tnr_adamw_step (clip and guard as before);
+        all off (None, 0): the calls, kernels, bits and buffers of a step without them."""
         clip_on = max_grad_norm is not None and max_grad_norm > 0
+        wd = float(weight_decay or 0.0)
+        W_, Td = int(warmup_steps or 0), int(lr_decay_steps or 0)
+        assert wd >= 0.0 and W_ >= 0 and Td >= 0, "weight_decay, warmup_steps and lr_decay_steps must not be negative"
+        sched_on = W_ > 0 or Td > 0
+        adamw_on = wd > 0.0 or sched_on
         sc = self.scaler
         guard, stamp = None, 0
         if sc.enabled:
@@ -1548,6 +1603,11 @@ class Engine:
             sc.stamp += 1
             guard, stamp = sc.guard, sc.stamp
         self.step_count += 1
+        if adamw_on:
+            # candidates k = 0, 1, 2: t_k = max(step_count - k, 1) updates taken including this one (the launcher's t_k)
+            mult = [lr_schedule(max(self.step_count - k, 1) - 1, W_, Td) for k in range(3)]
+            wbits = self._decay_bits() if wd > 0.0 else None
+        self.lr_scale = mult[0] if sched_on else None
         head0 = self.off(PFX + ("attn.att_fc1.weight" if self.cfg.pooling == "att" else "dense.weight"))   # end of the BERT layers
         e = self.off(PFX + "dense.bias") + self.slot[PFX + "dense.bias"][2]
         rest0 = min(_rup(e, 64), self.n_train)   # user encoders / transform matrices start here
@@ -1563,7 +1623,10 @@ class Engine:
             if hi_ > lo_:
                 args = (self.flat[True][lo_:hi_], self.flat_g[lo_:hi_], self.adam_m[lo_:hi_], self.adam_v[lo_:hi_],
                         self.adam_vmax[lo_:hi_] if amsgrad else None, hi_ - lo_, self.step_count, rate, beta1, beta2, eps, grad_scale)
-                if clip_on:
+                if adamw_on:
+                    T.call("tnr_adamw_step", *args[:7], rate * mult[0], rate * mult[1], rate * mult[2], beta1, beta2, eps, grad_scale,
+                           wd, wbits, lo_, guard, stamp, sc.skipped if guard is not None else 0, cs.clip if clip_on else None)
+                elif clip_on:
                     T.call("tnr_amsgrad_step_clipped", *args, guard, stamp, sc.skipped if guard is not None else 0, cs.clip)
                 elif guard is None:
                     T.call("tnr_amsgrad_step", *args)

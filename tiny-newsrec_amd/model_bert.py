@@ -329,14 +329,19 @@ class TnrAdam:
     """optim.Adam(model.parameters(), lr, amsgrad=True) of run.py:134 on the engine's flat buffers
     (one fused kernel + bf16-copy refresh); zero_grad / step keep the reference's call order (run.py:193-195)."""
 
-    def __init__(self, model, lr, grad_sync=None, pretrain_lr=None, pretrained_heads=False, max_grad_norm=0.0):
+    def __init__(self, model, lr, grad_sync=None, pretrain_lr=None, pretrained_heads=False, max_grad_norm=0.0,
+                 weight_decay=0.0, warmup_steps=0, lr_decay_steps=0):
         """pretrain_lr: PLM-NR/run.py:104-106 - the "pretrained" parameters step with their own rate: the encoder layers,
         and (pretrained_heads) the news encoder's pooling + dense when they came from the first-stage checkpoint too.
         max_grad_norm > 0: clip_grad_norm_ inside the engine's step, behind the gradient all-reduce (a clip_grad_norm_ between
-        backward() and step() would clip the un-reduced gradient); 0 = off."""
+        backward() and step() would clip the un-reduced gradient); 0 = off.
+        weight_decay / warmup_steps / lr_decay_steps: torch.optim.AdamW's decoupled decay (2-D weights outside LayerNorm) and the
+        linear warmup / decay of every rate, inside the fused update (Engine.step); all 0 = off, the reference's optimiser."""
         self.model, self.lr, self.grad_sync, self.pretrain_lr = model, lr, grad_sync, pretrain_lr
         self.pretrained_heads = pretrained_heads
         self.max_grad_norm = float(max_grad_norm or 0.0)
+        self.weight_decay, self.warmup_steps = float(weight_decay or 0.0), int(warmup_steps or 0)
+        self.lr_decay_steps = int(lr_decay_steps or 0)
 
     def zero_grad(self):
         pass                      # every backward overwrites the whole flat gradient buffer
@@ -346,4 +351,7 @@ class TnrAdam:
         # the engine waits for the gradient all-reduces bucket by bucket and updates each slice behind its own collective
         self.model.engine.step(self.lr, grad_scale=scale, lr_bert=self.pretrain_lr,
                                lr_news_head=self.pretrain_lr if self.pretrained_heads else None, sync=self.grad_sync,
-                               **({"max_grad_norm": self.max_grad_norm} if self.max_grad_norm > 0 else {}))
+                               **({"max_grad_norm": self.max_grad_norm} if self.max_grad_norm > 0 else {}),
+                               **({"weight_decay": self.weight_decay, "warmup_steps": self.warmup_steps,
+                                   "lr_decay_steps": self.lr_decay_steps}
+                                  if (self.weight_decay > 0 or self.warmup_steps > 0 or self.lr_decay_steps > 0) else {}))

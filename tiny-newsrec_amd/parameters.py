@@ -34,6 +34,9 @@ def _flag_table():
           # additions (defaults keep the reference behaviour)
           ("train_embeddings", _B, False, dict(help="also fine-tune bert.embeddings.* (word / position / token-type tables and the embedding LayerNorm) at the encoder's learning rate; the reference freezes them (run.py:101-112); needs --bert_trainable_layer")),
           ("max_grad_norm", float, 0.0, dict(help="clip the gradient by its global L2 norm, torch.nn.utils.clip_grad_norm_ semantics (one norm over everything trainable, coef = min(1, max_norm / (norm + 1e-6))), done on the device after the gradient all-reduce; 0 = off (the reference does not clip)")),
+          ("weight_decay", float, 0.0, dict(help="decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * weight_decay before the Adam / AMSGrad update) of the 2-D weights outside LayerNorm - biases, LayerNorm parameters and pad_doc are exempt; with --train_embeddings the embedding tables decay - inside the fused update; 0 = off (the reference uses Adam without decay)")),
+          ("warmup_steps", int, 0, dict(help="multiply every learning rate by u / warmup_steps over the first warmup_steps updates (u = updates taken so far: the first update has rate 0; steps skipped for an fp16 overflow do not count); 0 = no warmup (the reference's rate is constant). The schedule's position is optimiser state and, like the Adam moments, is not checkpointed")),
+          ("lr_decay_steps", int, 0, dict(help="after the warmup, decay every learning rate linearly to 0 at update lr_decay_steps (transformers' get_linear_schedule_with_warmup with num_training_steps = lr_decay_steps), 0 from there on; 0 = constant after the warmup (the reference's rate is constant). Not checkpointed, like the Adam moments")),
           ("resident_tables", _B, True, dict(help="keep news_combined / teacher tables in HBM and ship indices only")),
           ("cache_frozen_layers", _B, True, dict(help="resident mode: compute the frozen lower encoder layers once per news instead of every step (identical results)")),
           ("dedup_news", _B, True, dict(help="encode each distinct news of a batch once (resident mode; identical results)")),

@@ -64,6 +64,17 @@ def parse_args(argv=None):
     p.add_argument("--max_grad_norm", type=float, default=0.0,
                    help="clip the gradient by its global L2 norm, torch.nn.utils.clip_grad_norm_ semantics (one norm over the title + body "
                         "gradient of everything trainable), on the device after the gradient all-reduce; 0 = off (the notebooks do not clip)")
+    p.add_argument("--weight_decay", type=float, default=0.0,
+                   help="decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * weight_decay before the Adam update) of the 2-D weights "
+                        "outside LayerNorm (biases and LayerNorm parameters are exempt), inside the fused update; 0 = off (the notebooks "
+                        "use Adam without decay)")
+    p.add_argument("--warmup_steps", type=int, default=0,
+                   help="multiply both learning rates by u / warmup_steps over the first warmup_steps updates (u = updates taken so far: the "
+                        "first update has rate 0; steps skipped for an fp16 overflow do not count); 0 = no warmup (the notebooks' rates are "
+                        "constant). The schedule's position is optimiser state and, like the Adam moments, is not checkpointed")
+    p.add_argument("--lr_decay_steps", type=int, default=0,
+                   help="after the warmup, decay both learning rates linearly to 0 at update lr_decay_steps, 0 from there on; 0 = constant "
+                        "after the warmup (the notebooks' rates are constant). Not checkpointed, like the Adam moments")
     p.add_argument("--hidden_dropout_prob", type=float, default=None,
                    help="train-mode dropout (the notebooks call .train(): cell 19:6 / cell 16:6); default = the value in --config_name "
                         "(tnlrv3/config/*.json:4, 0.1), 0 turns it off")
@@ -233,6 +244,8 @@ def train(args):
             sums[4] += utils.acc(label, score)
             eng.backward(after_bucket=sync.launch if sync else None)
             clip_kw = {"max_grad_norm": args.max_grad_norm} if args.max_grad_norm > 0 else {}
+            if args.weight_decay > 0 or args.warmup_steps > 0 or args.lr_decay_steps > 0:
+                clip_kw = dict(clip_kw, weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps)
             eng.step(args.lr, grad_scale=sync.scale if sync else 1.0, lr_bert=args.pretrain_lr, amsgrad=False, sync=sync, **clip_kw)
             if args.stage == 0 and rank == 0 and cnt % args.save_steps == 0:          # cell 16: DP_12_layer_{cnt}.pt
                 os.makedirs(args.save_dir, exist_ok=True)
@@ -241,11 +254,12 @@ def train(args):
             if cnt % args.log_steps == 0:
                 s = (sums / cnt).tolist()
                 sc = eng.title.scaler
-                gn = eng.grad_norm() if clip_kw else None
-                logging.info("[%d] ed: %d, loss: %.5f, t_loss: %.5f, d_loss: %.5f, e_loss: %.5f, acc: %.5f, %.1f pairs/s%s%s" % (
+                gn = eng.grad_norm() if args.max_grad_norm > 0 else None
+                logging.info("[%d] ed: %d, loss: %.5f, t_loss: %.5f, d_loss: %.5f, e_loss: %.5f, acc: %.5f, %.1f pairs/s%s%s%s" % (
                     rank, cnt * B, s[0], s[1], s[2], s[3], s[4], size * cnt * B / max(time.time() - t0, 1e-9),
                     ", loss scale %g, %d steps skipped (fp16 overflow)" % (eng.title.gscale, sc.skipped) if sc.enabled and sc.skipped else "",
-                    ", grad norm {:g} (clip x{:.3g})".format(*gn) if gn is not None else ""))
+                    ", grad norm {:g} (clip x{:.3g})".format(*gn) if gn is not None else "",
+                    ", lr x{:.4g}".format(eng.lr_scale) if eng.lr_scale is not None else ""))
         if eng.title.scaler.enabled:
             eng.title.scaler.drain(eng.title)
         if rank == 0:

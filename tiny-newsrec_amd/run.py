@@ -92,7 +92,8 @@ def train(args):
     model._after_bucket = sync.launch if size > 1 else None
     optimizer = TnrAdam(model, args.lr, sync if size > 1 else None,
                         pretrain_lr=args.pretrain_lr if (plmnr and pretrained) else None,      # PLM-NR/run.py:94-106
-                        pretrained_heads=plmnr and pretrained, max_grad_norm=args.max_grad_norm)
+                        pretrained_heads=plmnr and pretrained, max_grad_norm=args.max_grad_norm,
+                        weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps)
 
     if args.synthetic:
         import synth
@@ -165,11 +166,13 @@ def train(args):
                 d = max(cnt, 1)
                 sc = eng.scaler          # fp16: steps whose 16-bit backward overflowed are skipped on the device (engine.LossScaler)
                 gn = eng.grad_norm() if args.max_grad_norm > 0 else None     # this step's norm after the all-reduce, and its clip
-                logging.info("[{}] Ed: {}, train_loss: {:.5f}, acc: {:.5f}, {:.1f} impressions/s{}{}".format(
+                logging.info("[{}] Ed: {}, train_loss: {:.5f}, acc: {:.5f}, {:.1f} impressions/s{}{}{}".format(
                     rank, cnt * args.batch_size, loss_sum.item() / d, acc_sum.item() / d,
                     size * cnt * args.batch_size / max(time.time() - t0, 1e-9),
                     ", loss scale {:g}, {} steps skipped (fp16 overflow)".format(eng.gscale, sc.skipped) if sc.enabled and sc.skipped else "",
-                    ", grad norm {:g} (clip x{:.3g})".format(*gn) if gn is not None else ""))
+                    ", grad norm {:g} (clip x{:.3g})".format(*gn) if gn is not None else "",
+                    # the host's schedule multiplier of the last step (the device may be up to two skipped steps behind it)
+                    ", lr x{:.4g}".format(eng.lr_scale) if eng.lr_scale is not None else ""))
         print(ep + 1)
         if eng.scaler.enabled:
             eng.scaler.drain(eng)        # the epoch's last two overflow answers, before the step count goes into a log line or a file

@@ -336,8 +336,15 @@ class Stage1Engine:
         return self.title.bucket_ranges()
 
     def step(self, lr, grad_scale=1.0, lr_bert=None, amsgrad=False, **kw):
-        """Post-train_KD.ipynb cell 18: optim.Adam([{bert_model, 1e-6}, {rest, 1e-5}]) (plain Adam by default here)."""
+        """Post-train_KD.ipynb cell 18: optim.Adam([{bert_model, 1e-6}, {rest, 1e-5}]) (plain Adam by default here).
+        kw: Engine.step's sync, max_grad_norm, weight_decay, warmup_steps, lr_decay_steps (one decay map, one schedule position:
+        the title engine owns the shared buffers)."""
         self.title.step(lr, grad_scale, lr_bert=lr_bert, amsgrad=amsgrad, **kw)
+
+    @property
+    def lr_scale(self):
+        """Engine.lr_scale of the last step(warmup_steps=, lr_decay_steps=): the host's schedule multiplier, None without one."""
+        return self.title.lr_scale
 
     def grad_norm(self):
         """Engine.grad_norm of the last step(max_grad_norm=...): one norm over the title + body gradient (one flat buffer)."""
