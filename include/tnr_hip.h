@@ -229,7 +229,8 @@ int tnr_attn_l32_bwd(const void* qkv, const float* mask_add, const float* rel, c
 
 /* The same attention for longer sequences (L <= 512: stage-1 title/body matching, Post-train_KD.ipynb cell 4-14):
  * flash-style 32-key tiles with an online softmax.  mask_add (N, Lr), rel (A, Lr, Lr) from tnr_embed_ln_fwd /
- * tnr_relpos_table with Lr = roundup(L, 32); lse (N, A, Lr) fp32 out (kept for backward). */
+ * tnr_relpos_table with Lr = roundup(L, 32); lse (N, A, Lr) fp32 out (kept for backward).  As for the l32 pair, qkv, ctx, dctx
+ * and dqkv must be 16-byte aligned (16-byte vector loads and stores): TNR_EINVAL otherwise. */
 int tnr_attn_long_fwd(const void* qkv, const float* mask_add, const float* rel, void* ctx, float* lse,
                       int64_t n_seq, int L, int A, void* stream);
 /* backward in two deterministic passes (dQ per query tile, dK/dV per key tile); delta (N, A, Lr) fp32 workspace */

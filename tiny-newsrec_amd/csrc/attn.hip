@@ -797,6 +797,7 @@ extern "C" int TNR_NAME(tnr_attn_long_fwd_do)(const void* qkv, const float* mask
     if (int rc = tnr_make_drop(drop, &dd, "tnr_attn_long_fwd")) return rc;
     TNR_CHECK_ARG(qkv && mask_add && rel && ctx && lse, "tnr_attn_long_fwd: null pointer");
     TNR_CHECK_ARG(L >= 1 && L <= 512 && A >= 1 && n_seq >= 1, "tnr_attn_long_fwd: need 1<=L<=512");
+    TNR_CHECK_ARG(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)ctx % 16) == 0, "tnr_attn_long_fwd: 16-byte alignment");
     const int Lr = (L + 31) / 32 * 32;
     int64_t items = n_seq * A * (Lr / 32);
     const int64_t blocks = n_seq * A * ((Lr / 32 + 3) / 4);      // one workgroup = four consecutive query tiles of one (sequence, head)
@@ -818,6 +819,8 @@ extern "C" int TNR_NAME(tnr_attn_long_bwd_do)(const void* qkv, const float* mask
     if (int rc = tnr_make_drop(drop, &dd, "tnr_attn_long_bwd")) return rc;
     TNR_CHECK_ARG(qkv && mask_add && rel && ctx && dctx && lse && delta && dqkv, "tnr_attn_long_bwd: null pointer");
     TNR_CHECK_ARG(L >= 1 && L <= 512 && A >= 1 && n_seq >= 1, "tnr_attn_long_bwd: need 1<=L<=512");
+    TNR_CHECK_ARG(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)ctx % 16) == 0 && ((uintptr_t)dctx % 16) == 0 &&
+                  ((uintptr_t)dqkv % 16) == 0, "tnr_attn_long_bwd: 16-byte alignment");
     const int Lr = (L + 31) / 32 * 32;
     int64_t items = n_seq * A * (Lr / 32);
     dim3 grid((unsigned)(n_seq * A * ((Lr / 32 + 3) / 4))), blk(256);      // one workgroup = four consecutive tiles of one (sequence, head)
