@@ -540,6 +540,24 @@ int tnr_adamw_step(float* p, const float* g, float* m, float* v, float* vmax, in
                    const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp, unsigned known_skips,
                    const float* clip, void* stream);
 
+/* An exponential moving average of the parameters inside the fused update: torch.optim.swa_utils.AveragedModel with
+ * get_ema_multi_avg_fn(decay) / TF's ExponentialMovingAverage (the reference has none; an extension, engine.py:
+ * Engine.step(ema_decay=, ema_warmup=)).  tnr_adamw_step_ema = tnr_adamw_step (guard, clip and decay_bits nullable under the same
+ * rules; lr0 == lr1 == lr2 with weight_decay == 0 is plain Adam / AMSGrad with an average) with
+ *   - ema: fp32, 16-byte aligned, laid out like p - the SAME slice of the average's buffer as p[0 .. n) is of the parameters'.
+ *     Once an element's new parameter p_new is formed (still in registers), ema <- ema + w_k (p_new - ema), one fma: +4 bytes
+ *     read and +4 written per element on the update's 36 (AMSGrad) or 28 (Adam).  p, m, v, vmax get the bits tnr_adamw_step gives.
+ *   - THREE weights w_k = 1 - decay_k in [0, 1], k = 0, 1, 2: the weight of this update if t_k = max(step - k, 1) updates have
+ *     been taken, this one included - picked on the device by guard[1] - known_skips together with lr_k and the bias corrections
+ *     (k >= 2 -> w2), so a warm-up of the decay (engine.ema_decay_at) follows the updates TAKEN.  The caller forms them in double
+ *     and rounds once.  w = 0 leaves the average's bits; w = 1 gives p_new up to the rounding of the difference.
+ *   - A launch stamped guard[0] (the skipped step) returns before touching ema: a skipped step does not advance the average.
+ * Errors (no launch): ema == NULL or not 16-byte aligned, a w_k outside [0, 1] or NaN, and everything tnr_adamw_step refuses. */
+int tnr_adamw_step_ema(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr0, float lr1,
+                       float lr2, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                       const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp, unsigned known_skips,
+                       const float* clip, float* ema, float w0, float w1, float w2, void* stream);
+
 /* refresh bf16 weight copies after an update: desc = n_desc * 8 int64 on DEVICE:
  * {src fp32 ptr, rows, cols, dst ptr (or 0), dst ld, dstT ptr (or 0), dstT ld, unused}
  * dst[r*ld + c] = bf16(src[r,c]) ; dstT[c*ldT + r] = bf16(src[r,c]), round to nearest even.  Only [0, rows) x [0, cols) of

@@ -19,6 +19,10 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 // would no longer be, instruction for instruction, the kernels they were.
 struct AdamFactors { float lr_c1[3], inv_sqrt_c2[3]; unsigned known_skips; };
 struct AdamDecay { float lr_wd[3]; };
+// The exponential moving average of the parameters (tnr_adamw_step_ema), behind AdamDecay for the same reason: e = the fp32 buffer
+// of the averages, laid out like p (the same slice of it), w[k] = 1 - decay of candidate k (a warm-up of the decay follows the
+// updates TAKEN, like the rates).
+struct AdamEma { float* e; float w[3]; };
 // CLIP: the gradient is scaled by gscale * clip[0], the coefficient grad_clip_commit_kernel left on the device (global-norm
 // clipping); without it `clip` is never read and the kernel is the unclipped one.
 // WD: decoupled weight decay in torch.optim.AdamW's order - p *= 1 - lr_k wd first, then the update on the undecayed gradient
@@ -26,23 +30,29 @@ struct AdamDecay { float lr_wd[3]; };
 // element of the WHOLE flat buffer, bit (e & 31) of word e >> 5, this launch's slice starting at element `first` of it.  first and
 // a thread's offset are multiples of 4, so its four bits are one nibble of one word.  Without WD neither wbits, first nor lr_wd is
 // read and the kernel is the one without decay.  A launch stamped guard[0] decays nothing.
-template <bool AMS, bool CLIP, bool WD>
+// EMA: once p_new is formed, e <- e + w_k (p_new - e) (one fma), e read and written like p: 16 bytes in the vector body, scalars
+// in the tail; +8 bytes per element on 36 (AMSGrad) or 28 (Adam).  A launch stamped guard[0] returns before touching e.  Without
+// EMA `a` is never read and the kernel is the one without the average.
+template <bool AMS, bool CLIP, bool WD, bool EMA>
 __global__ __launch_bounds__(256) void amsgrad_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v,
                                                       float* __restrict__ vmax, int64_t n, AdamFactors f,
                                                       float b1, float b2, float eps, float gscale,
                                                       const unsigned* __restrict__ guard, unsigned stamp,
                                                       const float* __restrict__ clip,
-                                                      const unsigned* __restrict__ wbits, int64_t first, AdamDecay d) {
+                                                      const unsigned* __restrict__ wbits, int64_t first, AdamDecay d,
+                                                      AdamEma a) {
     if (CLIP) gscale *= clip[0];
-    float lr_c1 = f.lr_c1[0], inv_sqrt_c2 = f.inv_sqrt_c2[0], keep = 1.f;
+    float lr_c1 = f.lr_c1[0], inv_sqrt_c2 = f.inv_sqrt_c2[0], keep = 1.f, w = 0.f;
     if (WD) keep = 1.f - d.lr_wd[0];
+    if (EMA) w = a.w[0];
     if (guard) {
         if (guard[0] == stamp) return;
         const unsigned k = guard[1] - f.known_skips;
-        if (k == 1) { lr_c1 = f.lr_c1[1]; inv_sqrt_c2 = f.inv_sqrt_c2[1]; if (WD) keep = 1.f - d.lr_wd[1]; }
-        else if (k >= 2) { lr_c1 = f.lr_c1[2]; inv_sqrt_c2 = f.inv_sqrt_c2[2]; if (WD) keep = 1.f - d.lr_wd[2]; }
+        if (k == 1) { lr_c1 = f.lr_c1[1]; inv_sqrt_c2 = f.inv_sqrt_c2[1]; if (WD) keep = 1.f - d.lr_wd[1]; if (EMA) w = a.w[1]; }
+        else if (k >= 2) { lr_c1 = f.lr_c1[2]; inv_sqrt_c2 = f.inv_sqrt_c2[2]; if (WD) keep = 1.f - d.lr_wd[2]; if (EMA) w = a.w[2]; }
     }
+    float* __restrict__ e = EMA ? a.e : nullptr;
     int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
     unsigned nib = 0;                       // bit r: element i + r decays (i < n, so the word lies inside the map)
@@ -54,16 +64,20 @@ __global__ __launch_bounds__(256) void amsgrad_kernel(float* __restrict__ p, con
         f32x4 vm = vv;
         if (AMS) vm = *(const f32x4*)(vmax + i);
         f32x4 pv = *(const f32x4*)(p + i);
+        f32x4 ev = pv;
+        if (EMA) ev = *(const f32x4*)(e + i);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (AMS) vm[r] = fmaxf(vm[r], vv[r]);
             if (WD) pv[r] = (nib >> r) & 1u ? pv[r] * keep : pv[r];
             pv[r] -= lr_c1 * (mv[r] / (sqrtf(vm[r]) * inv_sqrt_c2 + eps));
+            if (EMA) ev[r] = __builtin_fmaf(w, pv[r] - ev[r], ev[r]);
         }
         *(f32x4*)(m + i) = mv;
         *(f32x4*)(v + i) = vv;
         if (AMS) *(f32x4*)(vmax + i) = vm;
         *(f32x4*)(p + i) = pv;
+        if (EMA) *(f32x4*)(e + i) = ev;
     } else {
         for (; i < n; ++i, nib >>= 1) {
             float gv = g[i] * gscale;
@@ -74,7 +88,9 @@ __global__ __launch_bounds__(256) void amsgrad_kernel(float* __restrict__ p, con
             if (AMS) vmax[i] = vm;
             float pv = p[i];
             if (WD) pv = nib & 1u ? pv * keep : pv;
-            p[i] = pv - lr_c1 * (mv / (sqrtf(vm) * inv_sqrt_c2 + eps));
+            pv -= lr_c1 * (mv / (sqrtf(vm) * inv_sqrt_c2 + eps));
+            p[i] = pv;
+            if (EMA) e[i] = __builtin_fmaf(w, pv - e[i], e[i]);
         }
     }
 }
@@ -211,11 +227,12 @@ extern "C" int tnr_grad_nonfinite(const float* g, int64_t n, unsigned* guard, un
     return TNR_OK;
 }
 
-// lr[k]: the learning rate of candidate k (all three equal without a schedule); weight_decay > 0 needs the decay map.
+// lr[k]: the learning rate of candidate k (all three equal without a schedule); weight_decay > 0 needs the decay map; ema: the
+// average's buffer and its three weights, or NULL for the update without an average.
 static int amsgrad_launch(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, const float* lr,
                           float beta1, float beta2, float eps, float grad_scale, const unsigned* guard, unsigned stamp,
                           unsigned known_skips, const float* clip, float weight_decay, const unsigned* decay_bits, int64_t first,
-                          void* stream) {
+                          const AdamEma* ema, void* stream) {
     TNR_CHECK_ARG(p && g && m && v && n >= 1 && step >= 1, "tnr_amsgrad_step: bad argument");     // vmax NULL = plain Adam
     TNR_CHECK_ARG(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
                       ((uintptr_t)v % 16) == 0 && ((uintptr_t)vmax % 16) == 0, "tnr_amsgrad_step: 16-byte alignment");
@@ -230,13 +247,16 @@ static int amsgrad_launch(float* p, const float* g, float* m, float* v, float* v
         d.lr_wd[k] = (float)((double)lr[k] * (double)weight_decay);
     }
     f.known_skips = known_skips;
+    const AdamEma a = ema ? *ema : AdamEma{nullptr, {0.f, 0.f, 0.f}};
     int64_t nthr = (n + 3) / 4;
     const dim3 grid((unsigned)((nthr + 255) / 256));
-#define TNR_AMSGRAD_LAUNCH(AMS, CLIP, WD)                                                                                        \
-    hipLaunchKernelGGL((amsgrad_kernel<AMS, CLIP, WD>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, f, beta1, \
-                       beta2, eps, grad_scale, guard, stamp, clip, decay_bits, first, d)
+#define TNR_AMSGRAD_LAUNCH(AMS, CLIP, WD, EMA)                                                                                   \
+    hipLaunchKernelGGL((amsgrad_kernel<AMS, CLIP, WD, EMA>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, f,    \
+                       beta1, beta2, eps, grad_scale, guard, stamp, clip, decay_bits, first, d, a)
+#define TNR_AMSGRAD_LAUNCH_EMA(AMS, CLIP, WD)                                                                                    \
+    do { if (ema) TNR_AMSGRAD_LAUNCH(AMS, CLIP, WD, true); else TNR_AMSGRAD_LAUNCH(AMS, CLIP, WD, false); } while (0)
 #define TNR_AMSGRAD_LAUNCH_WD(AMS, CLIP)                                                                                         \
-    do { if (wd) TNR_AMSGRAD_LAUNCH(AMS, CLIP, true); else TNR_AMSGRAD_LAUNCH(AMS, CLIP, false); } while (0)
+    do { if (wd) TNR_AMSGRAD_LAUNCH_EMA(AMS, CLIP, true); else TNR_AMSGRAD_LAUNCH_EMA(AMS, CLIP, false); } while (0)
     if (vmax) {
         if (clip) TNR_AMSGRAD_LAUNCH_WD(true, true);
         else TNR_AMSGRAD_LAUNCH_WD(true, false);
@@ -245,6 +265,7 @@ static int amsgrad_launch(float* p, const float* g, float* m, float* v, float* v
         else TNR_AMSGRAD_LAUNCH_WD(false, false);
     }
 #undef TNR_AMSGRAD_LAUNCH_WD
+#undef TNR_AMSGRAD_LAUNCH_EMA
 #undef TNR_AMSGRAD_LAUNCH
     TNR_CHECK_LAUNCH("tnr_amsgrad_step");
     return TNR_OK;
@@ -255,7 +276,7 @@ extern "C" int tnr_amsgrad_step_guarded(float* p, const float* g, float* m, floa
                                         unsigned stamp, unsigned known_skips, void* stream) {
     const float lrs[3] = {lr, lr, lr};
     return amsgrad_launch(p, g, m, v, vmax, n, step, lrs, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, nullptr, 0.f,
-                          nullptr, 0, stream);
+                          nullptr, 0, nullptr, stream);
 }
 
 extern "C" int tnr_amsgrad_step_clipped(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
@@ -264,20 +285,41 @@ extern "C" int tnr_amsgrad_step_clipped(float* p, const float* g, float* m, floa
     TNR_CHECK_ARG(clip && ((uintptr_t)clip % 4) == 0, "tnr_amsgrad_step_clipped: clip must point at the two floats of tnr_grad_clip_commit");
     const float lrs[3] = {lr, lr, lr};
     return amsgrad_launch(p, g, m, v, vmax, n, step, lrs, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, clip, 0.f,
-                          nullptr, 0, stream);
+                          nullptr, 0, nullptr, stream);
 }
 
-extern "C" int tnr_adamw_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr0, float lr1,
-                              float lr2, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
-                              const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp,
-                              unsigned known_skips, const float* clip, void* stream) {
+// tnr_adamw_step and tnr_adamw_step_ema (ema != NULL): one set of checks, one launcher
+static int adamw_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr0, float lr1,
+                      float lr2, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                      const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp, unsigned known_skips,
+                      const float* clip, const AdamEma* ema, void* stream) {
     TNR_CHECK_ARG(weight_decay >= 0.f && (weight_decay == 0.f || decay_bits) && ((uintptr_t)decay_bits % 4) == 0,
                   "tnr_adamw_step: weight_decay > 0 needs the decay map (and none below 0)");
     TNR_CHECK_ARG(first >= 0 && first % 4 == 0, "tnr_adamw_step: first must be a multiple of 4 (a thread's four bits in one word)");
     TNR_CHECK_ARG(((uintptr_t)clip % 4) == 0, "tnr_adamw_step: clip must point at the two floats of tnr_grad_clip_commit");
     const float lrs[3] = {lr0, lr1, lr2};
     return amsgrad_launch(p, g, m, v, vmax, n, step, lrs, beta1, beta2, eps, grad_scale, guard, stamp, known_skips, clip,
-                          weight_decay, decay_bits, first, stream);
+                          weight_decay, decay_bits, first, ema, stream);
+}
+
+extern "C" int tnr_adamw_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr0, float lr1,
+                              float lr2, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                              const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp,
+                              unsigned known_skips, const float* clip, void* stream) {
+    return adamw_step(p, g, m, v, vmax, n, step, lr0, lr1, lr2, beta1, beta2, eps, grad_scale, weight_decay, decay_bits, first,
+                      guard, stamp, known_skips, clip, nullptr, stream);
+}
+
+extern "C" int tnr_adamw_step_ema(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr0,
+                                  float lr1, float lr2, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                                  const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp,
+                                  unsigned known_skips, const float* clip, float* ema, float w0, float w1, float w2, void* stream) {
+    TNR_CHECK_ARG(ema && ((uintptr_t)ema % 16) == 0, "tnr_adamw_step_ema: ema must be a 16-byte aligned buffer laid out like p");
+    TNR_CHECK_ARG(w0 >= 0.f && w0 <= 1.f && w1 >= 0.f && w1 <= 1.f && w2 >= 0.f && w2 <= 1.f,     // false for a NaN
+                  "tnr_adamw_step_ema: every weight 1 - decay must lie in [0, 1]");
+    const AdamEma a = {ema, {w0, w1, w2}};
+    return adamw_step(p, g, m, v, vmax, n, step, lr0, lr1, lr2, beta1, beta2, eps, grad_scale, weight_decay, decay_bits, first,
+                      guard, stamp, known_skips, clip, &a, stream);
 }
 
 extern "C" int64_t tnr_grad_sumsq_parts(int64_t n) { return sumsq_grid(n); }

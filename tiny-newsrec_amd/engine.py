@@ -239,6 +239,14 @@ def lr_schedule(u, warmup_steps=0, lr_decay_steps=0):
     return 1.0
 
 
+def ema_decay_at(u, decay, warmup=False):
+    """Decay of the parameter average at an update that `u` updates precede (step(ema_decay=decay, ema_warmup=warmup)):
+    `decay`, or with warmup min(decay, (1 + u) / (10 + u)) - TF's ExponentialMovingAverage(num_updates=u) rule: the first updates
+    weigh in heavily (0.1, 0.18, 0.25, ...), so the average leaves its starting point as fast as the parameters do."""
+    u, decay = int(u), float(decay)
+    return min(decay, (1.0 + u) / (10.0 + u)) if warmup else decay
+
+
 def decays(name, shape):
     """The decay set of step(weight_decay=...): 2-D `.weight`s outside LayerNorm (Linear and embedding matrices); biases, every
     LayerNorm parameter and pad_doc are exempt."""
@@ -357,6 +365,8 @@ class Engine:
         self._clip_state = None
         self._decay_map = None       # step(weight_decay > 0): the owner's decay bits on the device, made on first use
         self.lr_scale = None         # the host's multiplier of the last step's learning rates while a schedule is on, else None
+        self._ema = None             # step(ema_decay > 0): the owner's average of flat[True], made on first use
+        self._ema_updates = [0, 0]   # updates counted into it, and the scaler's skipped-step total that count already reflects
         self.max_batch = max_batch
         self.extra_rows, self.extra_seqs = int(extra_rows), int(extra_seqs)
         self.drop = None             # set_dropout(): train-mode dropout of the stage-0 / stage-1 notebooks
@@ -1562,8 +1572,58 @@ class Engine:
             own._decay_map = torch.from_numpy(words.view(np.int32)).to(own.dev)
         return own._decay_map
 
+    def _ema_buffer(self):
+        """The average of flat[True] (step(ema_decay > 0)): fp32, laid out like flat[True], made on first use by the engine that
+        owns flat[True] as a copy of the parameters as they are now, on the current stream (the first step with the average on
+        calls this before its update); engines built with share= use the owner's."""
+        own = self._clip_owner
+        if own._ema is None:
+            own._ema = own.flat[True].clone()
+            own.ema_updates = 0
+        return own._ema
+
+    @property
+    def ema_updates(self):
+        """How many updates the average has taken (settable: a checkpoint's count).  Steps the fp16 guard skipped are taken out as
+        the host hears of them, like Adam's count: exact once the scaler is drained."""
+        own = self._clip_owner
+        return own._ema_updates[0] - (own.scaler.skipped - own._ema_updates[1])
+
+    @ema_updates.setter
+    def ema_updates(self, n):
+        own = self._clip_owner
+        own._ema_updates = [int(n), own.scaler.skipped]
+
+    def ema_state_dict(self):
+        """The reference-keyed state dict of the AVERAGED model: trainable parameters from the average, frozen ones (teachers,
+        frozen layers, embeddings) from flat[False], exactly as state_dict() has them.  None if no step ever ran with ema_decay
+        and nothing was loaded."""
+        ema = self._clip_owner._ema
+        if ema is None:
+            return None
+        out = {}
+        for k, v in self.params.items():
+            tr, o, n, shp = self.slot[k]
+            out[k] = (ema[o:o + n].view(shp) if tr else v).detach().clone()
+        return out
+
+    def load_ema_state_dict(self, sd):
+        """Write the trainable slots of the average from a state dict with the reference's keys (ema_state_dict()'s), making the
+        buffer if there is none yet (what lies between the slots starts as the parameters' gaps).  Frozen keys are ignored: they
+        have no average.  load_state_dict() never touches the average."""
+        ema = self._ema_buffer()
+        for k, (tr, o, n, shp) in self.slot.items():
+            if not tr:
+                continue
+            if k not in sd:
+                raise KeyError("missing key: %s" % k)
+            v = sd[k] if isinstance(sd[k], torch.Tensor) else torch.as_tensor(sd[k])
+            if tuple(v.shape) != tuple(shp):
+                raise ValueError("%s: shape %s != %s" % (k, tuple(v.shape), shp))
+            ema[o:o + n].view(shp).copy_(v.to(self.dev, torch.float32))
+
     def step(self, lr, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, lr_bert=None, amsgrad=True, lr_news_head=None, sync=None,
-             max_grad_norm=None, weight_decay=0.0, warmup_steps=0, lr_decay_steps=0):
+             max_grad_norm=None, weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=None, ema_warmup=False):
         """torch.optim.Adam(amsgrad=True).step() (run.py:134,195) + refresh of the 16-bit weight copies.
         lr_bert / lr_news_head: learning rates of the encoder layers / of the news encoder's pooling + dense when they
         differ (PLM-NR/run.py:104-106: {'params': pretrained, 'lr': pretrain_lr}, {'params': rest, 'lr': lr}; the notebooks
@@ -1588,8 +1648,21 @@ class Engine:
         beside the three bias corrections and picks by the skips the host has not accounted for, so a skipped step advances
         neither Adam's count nor the schedule and decays nothing.  The position is optimiser state (not checkpointed, like m, v,
         vmax).  With any of the three on, every range / bucket launch goes through tnr_adamw_step (clip and guard as before);
-        all off (None, 0): the calls, kernels, bits and buffers of a step without them."""
+        all off (None, 0): the calls, kernels, bits and buffers of a step without them.
+        ema_decay = d in (0, 1]: an exponential moving average of the trainable parameters, ema <- d ema + (1 - d) p_new inside the
+        update kernel (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(d)), in an fp32 buffer laid out like flat[True]
+        that the owner of flat[True] makes on the first such step as a copy of the parameters BEFORE that update (engines built
+        with share= use it).  Every range / bucket launch then goes through tnr_adamw_step_ema on all three paths (elementwise:
+        the same bits on each).  ema_warmup: d(u) = min(d, (1 + u) / (10 + u)) (ema_decay_at), u = the updates TAKEN before this
+        one, from the step_count the bias corrections use - the kernel gets the weights 1 - d of u, u - 1, u - 2 and picks as it
+        picks the rates, and a step the fp16 guard skips leaves the average's bits.  Data parallelism has nothing to communicate:
+        the average is an elementwise function of parameters that are identical on every rank, so it is identical too.
+        ema_state_dict() / load_ema_state_dict() read and write it; load_state_dict() does not touch it.  None or <= 0: off - the
+        calls, kernels, bits and buffers of a step without it."""
         clip_on = max_grad_norm is not None and max_grad_norm > 0
+        ema_d = float(ema_decay or 0.0)
+        ema_on = ema_d > 0.0
+        assert ema_d <= 1.0, "ema_decay must not exceed 1"
         wd = float(weight_decay or 0.0)
         W_, Td = int(warmup_steps or 0), int(lr_decay_steps or 0)
         assert wd >= 0.0 and W_ >= 0 and Td >= 0, "weight_decay, warmup_steps and lr_decay_steps must not be negative"
@@ -1607,7 +1680,14 @@ class Engine:
             # candidates k = 0, 1, 2: t_k = max(step_count - k, 1) updates taken including this one (the launcher's t_k)
             mult = [lr_schedule(max(self.step_count - k, 1) - 1, W_, Td) for k in range(3)]
             wbits = self._decay_bits() if wd > 0.0 else None
+        elif ema_on:
+            mult, wbits = (1.0, 1.0, 1.0), None
         self.lr_scale = mult[0] if sched_on else None
+        if ema_on:
+            ema = self._ema_buffer()                 # first time: the parameters as they are before this update
+            self.ema_updates += 1
+            # formed in double, rounded once (by the float argument)
+            ema_w = [1.0 - ema_decay_at(max(self.step_count - k, 1) - 1, ema_d, ema_warmup) for k in range(3)]
         head0 = self.off(PFX + ("attn.att_fc1.weight" if self.cfg.pooling == "att" else "dense.weight"))   # end of the BERT layers
         e = self.off(PFX + "dense.bias") + self.slot[PFX + "dense.bias"][2]
         rest0 = min(_rup(e, 64), self.n_train)   # user encoders / transform matrices start here
@@ -1623,7 +1703,11 @@ class Engine:
             if hi_ > lo_:
                 args = (self.flat[True][lo_:hi_], self.flat_g[lo_:hi_], self.adam_m[lo_:hi_], self.adam_v[lo_:hi_],
                         self.adam_vmax[lo_:hi_] if amsgrad else None, hi_ - lo_, self.step_count, rate, beta1, beta2, eps, grad_scale)
-                if adamw_on:
+                if ema_on:
+                    T.call("tnr_adamw_step_ema", *args[:7], rate * mult[0], rate * mult[1], rate * mult[2], beta1, beta2, eps,
+                           grad_scale, wd, wbits, lo_, guard, stamp, sc.skipped if guard is not None else 0,
+                           cs.clip if clip_on else None, ema[lo_:hi_], ema_w[0], ema_w[1], ema_w[2])
+                elif adamw_on:
                     T.call("tnr_adamw_step", *args[:7], rate * mult[0], rate * mult[1], rate * mult[2], beta1, beta2, eps, grad_scale,
                            wd, wbits, lo_, guard, stamp, sc.skipped if guard is not None else 0, cs.clip if clip_on else None)
                 elif clip_on:

@@ -236,6 +236,18 @@ class Model(_Shell):
         self.engine.refresh_shadows(all_layers=True)       # bf16 copies + rel-pos table follow the fp32 weights
         return out
 
+    def ema_state_dict(self):
+        """state_dict() of the averaged model (Engine.step(ema_decay=...)): the same keys in the same order, trainable parameters
+        from the engine's average, frozen ones equal to state_dict()'s.  None if the average was never on."""
+        esd = self.engine.ema_state_dict()
+        if esd is None:
+            return None
+        return {k: esd[self._engine_key(k)] for k in self.state_dict()}
+
+    def load_ema_state_dict(self, sd):
+        """The average resumes from a checkpoint's ema_state_dict (this model's keys); the parameters are not touched."""
+        self.engine.load_ema_state_dict({self._engine_key(k): v for k, v in sd.items()})
+
     def forward(self, history, history_mask, candidate, label, teacher_history_embs, teacher_candidate_embs):
         eng = self.engine
         if isinstance(history, tuple) and len(history) == 4:      # resident-mode IndexBatch
@@ -330,18 +342,21 @@ class TnrAdam:
     (one fused kernel + bf16-copy refresh); zero_grad / step keep the reference's call order (run.py:193-195)."""
 
     def __init__(self, model, lr, grad_sync=None, pretrain_lr=None, pretrained_heads=False, max_grad_norm=0.0,
-                 weight_decay=0.0, warmup_steps=0, lr_decay_steps=0):
+                 weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=0.0, ema_warmup=False):
         """pretrain_lr: PLM-NR/run.py:104-106 - the "pretrained" parameters step with their own rate: the encoder layers,
         and (pretrained_heads) the news encoder's pooling + dense when they came from the first-stage checkpoint too.
         max_grad_norm > 0: clip_grad_norm_ inside the engine's step, behind the gradient all-reduce (a clip_grad_norm_ between
         backward() and step() would clip the un-reduced gradient); 0 = off.
         weight_decay / warmup_steps / lr_decay_steps: torch.optim.AdamW's decoupled decay (2-D weights outside LayerNorm) and the
-        linear warmup / decay of every rate, inside the fused update (Engine.step); all 0 = off, the reference's optimiser."""
+        linear warmup / decay of every rate, inside the fused update (Engine.step); all 0 = off, the reference's optimiser.
+        ema_decay > 0 (ema_warmup: TF's warm-up of the decay): an exponential moving average of the trainable parameters kept by
+        the same kernel (Engine.step(ema_decay=, ema_warmup=), model.ema_state_dict()); 0 = off, no average, no buffer."""
         self.model, self.lr, self.grad_sync, self.pretrain_lr = model, lr, grad_sync, pretrain_lr
         self.pretrained_heads = pretrained_heads
         self.max_grad_norm = float(max_grad_norm or 0.0)
         self.weight_decay, self.warmup_steps = float(weight_decay or 0.0), int(warmup_steps or 0)
         self.lr_decay_steps = int(lr_decay_steps or 0)
+        self.ema_decay, self.ema_warmup = float(ema_decay or 0.0), bool(ema_warmup)
 
     def zero_grad(self):
         pass                      # every backward overwrites the whole flat gradient buffer
@@ -354,4 +369,5 @@ class TnrAdam:
                                **({"max_grad_norm": self.max_grad_norm} if self.max_grad_norm > 0 else {}),
                                **({"weight_decay": self.weight_decay, "warmup_steps": self.warmup_steps,
                                    "lr_decay_steps": self.lr_decay_steps}
-                                  if (self.weight_decay > 0 or self.warmup_steps > 0 or self.lr_decay_steps > 0) else {}))
+                                  if (self.weight_decay > 0 or self.warmup_steps > 0 or self.lr_decay_steps > 0) else {}),
+                               **({"ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup} if self.ema_decay > 0 else {}))

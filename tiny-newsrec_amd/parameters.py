@@ -37,6 +37,9 @@ def _flag_table():
           ("weight_decay", float, 0.0, dict(help="decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * weight_decay before the Adam / AMSGrad update) of the 2-D weights outside LayerNorm - biases, LayerNorm parameters and pad_doc are exempt; with --train_embeddings the embedding tables decay - inside the fused update; 0 = off (the reference uses Adam without decay)")),
           ("warmup_steps", int, 0, dict(help="multiply every learning rate by u / warmup_steps over the first warmup_steps updates (u = updates taken so far: the first update has rate 0; steps skipped for an fp16 overflow do not count); 0 = no warmup (the reference's rate is constant). The schedule's position is optimiser state and, like the Adam moments, is not checkpointed")),
           ("lr_decay_steps", int, 0, dict(help="after the warmup, decay every learning rate linearly to 0 at update lr_decay_steps (transformers' get_linear_schedule_with_warmup with num_training_steps = lr_decay_steps), 0 from there on; 0 = constant after the warmup (the reference's rate is constant). Not checkpointed, like the Adam moments")),
+          ("ema_decay", float, 0.0, dict(help="keep an exponential moving average of the trainable parameters, ema = ema_decay * ema + (1 - ema_decay) * p after every update (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn), inside the fused update; steps skipped for an fp16 overflow do not advance it. The epoch checkpoint then also holds ema_state_dict (same keys as model_state_dict) and ema (decay, warmup, updates), and --load_ckpt_name resumes the average from it; 0 = off (the reference keeps no average)")),
+          ("ema_warmup", _B, False, dict(help="with --ema_decay: use min(ema_decay, (1 + u) / (10 + u)) at the update that u updates precede (TensorFlow's ExponentialMovingAverage num_updates rule), so that a short run's average is not dominated by its starting point. The position follows the updates taken and, like the Adam moments, is not checkpointed")),
+          ("use_ema", _B, False, dict(help="--mode test: evaluate the averaged parameters (the checkpoint's ema_state_dict, written by a --ema_decay run) instead of model_state_dict; an error if the checkpoint holds none")),
           ("resident_tables", _B, True, dict(help="keep news_combined / teacher tables in HBM and ship indices only")),
           ("cache_frozen_layers", _B, True, dict(help="resident mode: compute the frozen lower encoder layers once per news instead of every step (identical results)")),
           ("dedup_news", _B, True, dict(help="encode each distinct news of a batch once (resident mode; identical results)")),

@@ -75,6 +75,13 @@ def parse_args(argv=None):
     p.add_argument("--lr_decay_steps", type=int, default=0,
                    help="after the warmup, decay both learning rates linearly to 0 at update lr_decay_steps, 0 from there on; 0 = constant "
                         "after the warmup (the notebooks' rates are constant). Not checkpointed, like the Adam moments")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="keep an exponential moving average of the trainable parameters, ema = ema_decay * ema + (1 - ema_decay) * p after "
+                        "every update, inside the fused update (steps skipped for an fp16 overflow do not advance it); the checkpoint then "
+                        "also holds ema_state_dict and ema (decay, warmup, updates); 0 = off (the notebooks keep no average)")
+    p.add_argument("--ema_warmup", type=b, default=False,
+                   help="with --ema_decay: use min(ema_decay, (1 + u) / (10 + u)) at the update that u updates precede (TensorFlow's "
+                        "num_updates rule). Not checkpointed, like the Adam moments")
     p.add_argument("--hidden_dropout_prob", type=float, default=None,
                    help="train-mode dropout (the notebooks call .train(): cell 19:6 / cell 16:6); default = the value in --config_name "
                         "(tnlrv3/config/*.json:4, 0.1), 0 turns it off")
@@ -143,11 +150,22 @@ def _model_dims(args):
                 news_dim=args.news_dim, news_query=args.news_query_vector_dim)
 
 
-def _ckpt_state(eng, stage):
+def _ckpt_state(eng, stage, sd=None):
     """Checkpoint keys: DistillModel's (student.news_encoder.*, transform_matrix.*) for stage 1, TitleBodySimModel's
-    (news_encoder.*) for stage 0."""
-    sd = {k: v.cpu() for k, v in eng.state_dict().items()}
+    (news_encoder.*) for stage 0.  sd: another state dict of the engine's (the averaged model's) to put under the same keys."""
+    sd = {k: v.cpu() for k, v in (eng.state_dict() if sd is None else sd).items()}
     return sd if stage == 1 else {k[len("student."):]: v for k, v in sd.items()}
+
+
+def _ckpt(eng, args):
+    """What a checkpoint file holds: model_state_dict as the notebooks save it and, with --ema_decay, the averaged model and the
+    average's settings beside it."""
+    out = {"model_state_dict": _ckpt_state(eng, args.stage)}
+    esd = eng.ema_state_dict() if args.ema_decay > 0 else None
+    if esd is not None:
+        out["ema_state_dict"] = _ckpt_state(eng, args.stage, esd)
+        out["ema"] = {"decay": args.ema_decay, "warmup": bool(args.ema_warmup), "updates": eng.ema_updates}
+    return out
 
 
 def _load_ckpt(eng, path, stage):
@@ -246,10 +264,12 @@ def train(args):
             clip_kw = {"max_grad_norm": args.max_grad_norm} if args.max_grad_norm > 0 else {}
             if args.weight_decay > 0 or args.warmup_steps > 0 or args.lr_decay_steps > 0:
                 clip_kw = dict(clip_kw, weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps)
+            if args.ema_decay > 0:
+                clip_kw = dict(clip_kw, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
             eng.step(args.lr, grad_scale=sync.scale if sync else 1.0, lr_bert=args.pretrain_lr, amsgrad=False, sync=sync, **clip_kw)
             if args.stage == 0 and rank == 0 and cnt % args.save_steps == 0:          # cell 16: DP_12_layer_{cnt}.pt
                 os.makedirs(args.save_dir, exist_ok=True)
-                torch.save({"model_state_dict": _ckpt_state(eng, 0)},
+                torch.save(_ckpt(eng, args),
                            os.path.join(args.save_dir, "DP_%d_layer_%d.pt" % (args.num_hidden_layers, cnt)))
             if cnt % args.log_steps == 0:
                 s = (sums / cnt).tolist()
@@ -266,7 +286,7 @@ def train(args):
             os.makedirs(args.save_dir, exist_ok=True)
             name = "first_stage_%d_layer.pt" if args.stage == 1 else "DP_%d_layer.pt"
             path = os.path.join(args.save_dir, name % args.num_hidden_layers)
-            torch.save({"model_state_dict": _ckpt_state(eng, args.stage)}, path)
+            torch.save(_ckpt(eng, args), path)
             logging.info("Model saved to %s", path)
     return eng
 

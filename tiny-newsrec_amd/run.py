@@ -84,8 +84,13 @@ def train(args):
     model.load_state_dict(sd)
     if args.load_ckpt_name is not None:                                      # run.py:125-129
         ck = utils.get_checkpoint(args.model_dir, args.load_ckpt_name)
-        model.load_state_dict(torch.load(ck, map_location="cpu")["model_state_dict"])
+        loaded = torch.load(ck, map_location="cpu")
+        model.load_state_dict(loaded["model_state_dict"])
         logging.info(f"Model loaded from {ck}")
+        if args.ema_decay > 0 and "ema_state_dict" in loaded:      # the average resumes; without one it starts from the loaded parameters
+            model.load_ema_state_dict(loaded["ema_state_dict"])
+            eng.ema_updates = int(loaded.get("ema", {}).get("updates", 0))
+            logging.info(f"EMA of the weights resumed from {ck} ({eng.ema_updates} updates)")
     dist.broadcast_flat([eng.flat[True], eng.flat[False]])                   # hvd.broadcast_parameters, run.py:142
     eng.refresh_shadows(all_layers=True)
     sync = dist.GradSync(eng.flat_g, eng.bucket_ranges(), size)             # hvd.DistributedOptimizer(Average), :145-149
@@ -93,7 +98,8 @@ def train(args):
     optimizer = TnrAdam(model, args.lr, sync if size > 1 else None,
                         pretrain_lr=args.pretrain_lr if (plmnr and pretrained) else None,      # PLM-NR/run.py:94-106
                         pretrained_heads=plmnr and pretrained, max_grad_norm=args.max_grad_norm,
-                        weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps)
+                        weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps,
+                        ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
 
     if args.synthetic:
         import synth
@@ -179,8 +185,13 @@ def train(args):
         if rank == 0:                                                        # run.py:205-214
             os.makedirs(args.model_dir, exist_ok=True)
             ckpt_path = os.path.join(args.model_dir, f"epoch-{ep + 1}.pt")
-            torch.save({"model_state_dict": {k: v.cpu() for k, v in model.state_dict().items()},
-                        "category_dict": category_dict, "word_dict": None, "subcategory_dict": subcategory_dict}, ckpt_path)
+            ckpt = {"model_state_dict": {k: v.cpu() for k, v in model.state_dict().items()},
+                    "category_dict": category_dict, "word_dict": None, "subcategory_dict": subcategory_dict}
+            esd = model.ema_state_dict() if args.ema_decay > 0 else None
+            if esd is not None:          # --ema_decay: the averaged model beside the trained one, which stays what the reference loads
+                ckpt["ema_state_dict"] = {k: v.cpu() for k, v in esd.items()}
+                ckpt["ema"] = {"decay": args.ema_decay, "warmup": bool(args.ema_warmup), "updates": eng.ema_updates}
+            torch.save(ckpt, ckpt_path)
             logging.info(f"Model saved to {ckpt_path}")
     if not args.synthetic:
         loader.join()
@@ -241,9 +252,15 @@ def test(args, collect=None):
     size, rank, local = utils.init_hvd_cuda(args.enable_hvd, args.enable_gpu)
     ckpt_path = utils.get_checkpoint(args.model_dir, args.load_ckpt_name) if args.load_ckpt_name else utils.latest_checkpoint(args.model_dir)
     assert ckpt_path is not None, "No ckpt found"
-    sd = torch.load(ckpt_path, map_location="cpu")["model_state_dict"]
+    ckpt = torch.load(ckpt_path, map_location="cpu")
+    if getattr(args, "use_ema", False):
+        if "ema_state_dict" not in ckpt:
+            raise KeyError(f"--use_ema True: {ckpt_path} holds no ema_state_dict (it was not trained with --ema_decay)")
+        sd = ckpt["ema_state_dict"]
+    else:
+        sd = ckpt["model_state_dict"]
     eng = _forward_engine(args, args.num_student_layers, sd)
-    logging.info(f"Model loaded from {ckpt_path}")
+    logging.info(f"Model loaded from {ckpt_path}" + (" (the EMA of the weights)" if getattr(args, "use_ema", False) else ""))
     news_index, news_combined = _news_table(args, args.test_data_dir, "test")
     news_scoring = eng.encode_news(torch.from_numpy(news_combined).cuda())
     scoring_host = news_scoring.cpu().numpy()

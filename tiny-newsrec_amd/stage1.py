@@ -72,6 +72,17 @@ class Stage1Engine:
     def state_dict(self):
         return self.title.state_dict()
 
+    def ema_state_dict(self):
+        """Engine.ema_state_dict of the one average over the shared parameters (step(ema_decay=...)); None if it was never on."""
+        return self.title.ema_state_dict()
+
+    def load_ema_state_dict(self, sd):
+        self.title.load_ema_state_dict(sd)
+
+    @property
+    def ema_updates(self):
+        return self.title.ema_updates
+
     def grad(self, name):
         return self.title.grad(name)
 
@@ -337,8 +348,8 @@ class Stage1Engine:
 
     def step(self, lr, grad_scale=1.0, lr_bert=None, amsgrad=False, **kw):
         """Post-train_KD.ipynb cell 18: optim.Adam([{bert_model, 1e-6}, {rest, 1e-5}]) (plain Adam by default here).
-        kw: Engine.step's sync, max_grad_norm, weight_decay, warmup_steps, lr_decay_steps (one decay map, one schedule position:
-        the title engine owns the shared buffers)."""
+        kw: Engine.step's sync, max_grad_norm, weight_decay, warmup_steps, lr_decay_steps, ema_decay, ema_warmup (one decay map,
+        one schedule position, one average: the title engine owns the shared buffers)."""
         self.title.step(lr, grad_scale, lr_bert=lr_bert, amsgrad=amsgrad, **kw)
 
     @property
