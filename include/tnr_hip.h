@@ -516,6 +516,18 @@ int tnr_amsgrad_step_clipped(float* p, const float* g, float* m, float* v, float
                              float lr, float beta1, float beta2, float eps, float grad_scale, const unsigned* guard,
                              unsigned stamp, unsigned known_skips, const float* clip, void* stream);
 
+/* Gradient accumulation over micro-batches (the reference has none; an extension, engine.py: Engine.backward(micro=(j, K))).  One
+ * streaming pass over two fp32 buffers laid out alike (the flat gradient and an accumulator, or slices of them):
+ *   overwrite != 0:  dst[i] = src[i] for i in [0, n).  dst is NOT READ: whatever it held (an inf / nan of an abandoned window
+ *                    included) is gone, and the pass moves 8 bytes per element;
+ *   overwrite == 0:  dst[i] = dst[i] + src[i]: ONE IEEE fp32 add per element - no scale, no fma, nothing reassociated - so the
+ *                    bits are a function of the two inputs alone; 12 bytes per element.
+ * inf and nan propagate as IEEE addition propagates them (inf + -inf = nan), which is how an fp16 overflow in ANY micro-batch
+ * reaches the gradient the overflow guard scans.  The three uses: the first micro-batch (acc <- g), the ones between (acc += g)
+ * and the last (g += acc, dst the gradient buffer or one bucket's slice of it).  dst and src non-NULL, 16-byte aligned and
+ * different, n >= 1; anything else returns TNR_EINVAL and launches nothing.  Stream-ordered, no host synchronisation. */
+int tnr_grad_accum(float* dst, const float* src, int64_t n, int overwrite, void* stream);
+
 /* Decoupled weight decay and a learning-rate schedule in the fused update: torch.optim.AdamW(amsgrad = vmax != NULL) with
  * lr_scheduler.LambdaLR semantics (the reference has neither; an extension, engine.py: Engine.step(weight_decay=, warmup_steps=,
  * lr_decay_steps=)).  tnr_adamw_step = tnr_amsgrad_step_guarded / _clipped (guard and clip both nullable) with

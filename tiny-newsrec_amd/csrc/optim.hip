@@ -196,7 +196,49 @@ __global__ __launch_bounds__(256) void grad_clip_commit_kernel(const float* __re
     }
 }
 
+// Gradient accumulation over micro-batches (tnr_grad_accum): dst = src (OVERWRITE: dst is never read, so a stale inf / nan in it
+// cannot survive, and the pass moves 8 bytes per element) or dst = dst + src (12 bytes per element): one IEEE fp32 add per element,
+// no scale, no fma, nothing reassociated - the bits depend on the two inputs alone.  The memory shape of grad_nonfinite_kernel:
+// 16-byte accesses, four in flight per lane (eight loads when adding), 4096 elements per workgroup per trip of the grid-stride loop,
+// scalars in the last partial block.  dst and src never overlap (the host checks dst != src; slices of two different buffers).
+constexpr int ACCUM_GRID_CAP = 2048;
+template <bool OVERWRITE>
+__global__ __launch_bounds__(256) void grad_accum_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * 4096;
+    for (int64_t base = (int64_t)blockIdx.x * 4096; base < n; base += stride) {
+        const int64_t i0 = base + threadIdx.x * 4;
+        if (base + 4096 <= n) {
+            f32x4 s[4], d[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s[u] = *(const f32x4*)(src + i0 + u * 1024);
+            if (!OVERWRITE) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) d[u] = *(const f32x4*)(dst + i0 + u * 1024);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) s[u] = d[u] + s[u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) *(f32x4*)(dst + i0 + u * 1024) = s[u];
+        } else {
+            for (int u = 0; u < 4; ++u)
+                for (int64_t j = i0 + u * 1024; j < i0 + u * 1024 + 4 && j < n; ++j)
+                    dst[j] = OVERWRITE ? src[j] : dst[j] + src[j];
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int tnr_grad_accum(float* dst, const float* src, int64_t n, int overwrite, void* stream) {
+    TNR_CHECK_ARG(dst && src && n >= 1, "tnr_grad_accum: dst and src must not be NULL and n must be at least 1");
+    TNR_CHECK_ARG(((uintptr_t)dst % 16) == 0 && ((uintptr_t)src % 16) == 0, "tnr_grad_accum: 16-byte alignment");
+    TNR_CHECK_ARG(dst != src, "tnr_grad_accum: dst and src must be different buffers");
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 4095) / 4096, ACCUM_GRID_CAP);
+    if (overwrite) hipLaunchKernelGGL(grad_accum_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dst, src, n);
+    else hipLaunchKernelGGL(grad_accum_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dst, src, n);
+    TNR_CHECK_LAUNCH("tnr_grad_accum");
+    return TNR_OK;
+}
 
 extern "C" int tnr_amsgrad_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int step, float lr,
                                 float beta1, float beta2, float eps, float grad_scale, void* stream) {

@@ -367,6 +367,8 @@ class Engine:
         self.lr_scale = None         # the host's multiplier of the last step's learning rates while a schedule is on, else None
         self._ema = None             # step(ema_decay > 0): the owner's average of flat[True], made on first use
         self._ema_updates = [0, 0]   # updates counted into it, and the scaler's skipped-step total that count already reflects
+        self._acc = None             # backward(micro=(j, K > 1)): the owner's accumulator of flat_g over a window, made on first use
+        self._acc_held = 0           # micro-gradients the owner's accumulator holds (0 outside an accumulation window)
         self.max_batch = max_batch
         self.extra_rows, self.extra_seqs = int(extra_rows), int(extra_seqs)
         self.drop = None             # set_dropout(): train-mode dropout of the stage-0 / stage-1 notebooks
@@ -1202,9 +1204,26 @@ class Engine:
             self.red.clear()
             self._red_ginv = self.ginv
 
-    def backward(self, after_bucket=None):
+    def backward(self, after_bucket=None, micro=None):
         """d total_loss / d trainable parameters -> self.flat_g.  after_bucket(i) is called when gradient
-        bucket i (0 = heads, then one per layer from the top) is complete (dist.py overlaps its all-reduce)."""
+        bucket i (0 = heads, then one per layer from the top) is complete (dist.py overlaps its all-reduce).
+        micro = (j, K), K > 1: this is micro-batch j of a window of K whose gradients are SUMMED (gradient accumulation; the mean
+        is the caller's step(grad_scale = 1 / (world * K))).  Every backward still overwrites flat_g; the sum lives in an fp32
+        buffer of its own (_acc_buffer()) and moves by one tnr_grad_accum launch per micro-batch:
+          j < K - 1: backward WITHOUT the bucket hook, whatever after_bucket is - no collective starts (DistributedDataParallel's
+                     no_sync()) - then acc <- flat_g (j == 0: the accumulator is not read, nothing stale survives) or
+                     acc += flat_g over [0, n_train);
+          j == K - 1: flat_g += acc - with a hook bucket by bucket, flat_g[s:e] += acc[s:e] on the current stream in front of the
+                     caller's hook, so each bucket's collective (ordered behind the current stream by GradSync.launch) carries the
+                     window's sum; without one, a single launch over [0, n_train) behind backward (what lies between buckets is
+                     zero in both buffers: the same bits on every bucket element).
+        flat_g then holds ((g0 + g1) + ...) + g_{K-1}, one correctly rounded fp32 add per element and micro-batch, and the window
+        is closed.  j must be the number of micro-gradients held; step() inside a window is an error, accum_reset() drops one.
+        fp16: the dynamic loss scale only moves inside step(), so it is one value over the window, and an inf / nan in ANY
+        micro-batch's gradient reaches flat_g through the adds: step()'s scan then skips the WHOLE update as one skipped step.
+        micro = None or K == 1: the calls, bits and buffers of a backward without it."""
+        if micro is not None and int(micro[1]) > 1:
+            return self._backward_micro(after_bucket, int(micro[0]), int(micro[1]))
         self._red_check()
         cfg = self.cfg
         B, N, Rt = self.cur
@@ -1257,6 +1276,43 @@ class Engine:
             p = self.plan
             T.call("tnr_segment_sum_rows", dS, p.order, p.seg, p.n_enc, D, self.dSv)
             self.backward_encoder(self.dSv, p.n_enc, after_bucket=after_bucket)
+
+    def _backward_micro(self, after_bucket, j, K):
+        """backward(micro=(j, K)), K > 1 (its docstring)."""
+        own = self._clip_owner
+        assert 0 <= j < K, "micro = (j, K) needs 0 <= j < K"
+        assert j == own._acc_held, "micro-batch %d of %d, but the accumulator holds %d micro-gradients" % (j, K, own._acc_held)
+        acc = self._acc_buffer()
+        if j < K - 1:
+            self.backward()
+            T.call("tnr_grad_accum", acc, self.flat_g, self.n_train, 1 if j == 0 else 0)
+            own._acc_held = j + 1
+            return
+        if after_bucket is None:
+            self.backward()
+            T.call("tnr_grad_accum", self.flat_g, acc, self.n_train, 0)
+        else:
+            ranges = self.bucket_ranges()
+
+            def fold_then(b):
+                s_, e_ = ranges[b]
+                T.call("tnr_grad_accum", self.flat_g[s_:e_], acc[s_:e_], e_ - s_, 0)
+                after_bucket(b)
+            self.backward(after_bucket=fold_then)
+        own._acc_held = 0
+
+    def _acc_buffer(self):
+        """The accumulator of a gradient-accumulation window (backward(micro=...)): fp32, laid out like flat_g, made on first use
+        by the engine that owns flat_g; engines built with share= use the owner's.  Never requested, nothing is allocated."""
+        own = self._clip_owner
+        if own._acc is None:
+            own._acc = torch.zeros_like(own.flat_g)
+        return own._acc
+
+    def accum_reset(self):
+        """Drop a partial accumulation window (an epoch that ends inside one): the next backward(micro=(0, K)) overwrites
+        whatever the accumulator holds."""
+        self._clip_owner._acc_held = 0
 
     def _transform_grads(self, Rt, rb, pend=None):
         """dW_i = dP_i^T X_i ; db_i = colsum(dP_i)   (transform_matrix, model_bert.py:278,283).  The bias column sums ride in the
@@ -1658,7 +1714,11 @@ class Engine:
         picks the rates, and a step the fp16 guard skips leaves the average's bits.  Data parallelism has nothing to communicate:
         the average is an elementwise function of parameters that are identical on every rank, so it is identical too.
         ema_state_dict() / load_ema_state_dict() read and write it; load_state_dict() does not touch it.  None or <= 0: off - the
-        calls, kernels, bits and buffers of a step without it."""
+        calls, kernels, bits and buffers of a step without it.
+        Gradient accumulation (backward(micro=(j, K))) adds nothing here but an assertion: the window's mean is grad_scale =
+        1 / (world * K) on the summed flat_g, so the clip norm, the guard, the decay, the schedule and the average see what torch
+        shows them after K backwards of loss / K, with no extra pass."""
+        assert self._clip_owner._acc_held == 0, "step() inside an accumulation window"
         clip_on = max_grad_norm is not None and max_grad_norm > 0
         ema_d = float(ema_decay or 0.0)
         ema_on = ema_d > 0.0

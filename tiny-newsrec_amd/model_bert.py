@@ -158,7 +158,13 @@ class _Backward(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         m = ctx.model
-        m.engine.backward(after_bucket=m._after_bucket)
+        micro = getattr(m, "_micro", None)       # TnrAdam(grad_accum_steps=K > 1): (position in the window, K)
+        if micro is None:
+            m.engine.backward(after_bucket=m._after_bucket)
+        else:
+            if m.strict_grad_scale:
+                raise ValueError("strict_grad_scale cannot be combined with grad_accum_steps > 1")
+            m.engine.backward(after_bucket=m._after_bucket, micro=micro)
         if m.strict_grad_scale:
             m.engine.flat_g.mul_(gout)          # honour a non-unit upstream gradient (costs one pass)
         m._bind_grads()
@@ -201,6 +207,7 @@ class Model(_Shell):
         self._adopt(self.engine, "")
         self._anchor = torch.zeros(1, device=dev, requires_grad=True)
         self._after_bucket = None
+        self._micro = None           # set by TnrAdam(grad_accum_steps=K > 1): (position in the accumulation window, K)
         self.strict_grad_scale = False
         self._name_of = {id(p): k for k, p in self.named_parameters()}
         self.reset_parameters(getattr(args, "seed", 0) if getattr(args, "seed", None) is not None else 0)
@@ -342,7 +349,7 @@ class TnrAdam:
     (one fused kernel + bf16-copy refresh); zero_grad / step keep the reference's call order (run.py:193-195)."""
 
     def __init__(self, model, lr, grad_sync=None, pretrain_lr=None, pretrained_heads=False, max_grad_norm=0.0,
-                 weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=0.0, ema_warmup=False):
+                 weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=0.0, ema_warmup=False, grad_accum_steps=1):
         """pretrain_lr: PLM-NR/run.py:104-106 - the "pretrained" parameters step with their own rate: the encoder layers,
         and (pretrained_heads) the news encoder's pooling + dense when they came from the first-stage checkpoint too.
         max_grad_norm > 0: clip_grad_norm_ inside the engine's step, behind the gradient all-reduce (a clip_grad_norm_ between
@@ -350,19 +357,46 @@ class TnrAdam:
         weight_decay / warmup_steps / lr_decay_steps: torch.optim.AdamW's decoupled decay (2-D weights outside LayerNorm) and the
         linear warmup / decay of every rate, inside the fused update (Engine.step); all 0 = off, the reference's optimiser.
         ema_decay > 0 (ema_warmup: TF's warm-up of the decay): an exponential moving average of the trainable parameters kept by
-        the same kernel (Engine.step(ema_decay=, ema_warmup=), model.ema_state_dict()); 0 = off, no average, no buffer."""
+        the same kernel (Engine.step(ema_decay=, ema_warmup=), model.ema_state_dict()); 0 = off, no average, no buffer.
+        grad_accum_steps = K > 1: one update per K calls of backward() / step() on the MEAN gradient of the K batches.  The optimiser
+        owns the position in the window and publishes (j, K) on the model, whose backward hands it to Engine.backward(micro=):
+        the engine sums the K gradients (under data parallelism the all-reduces start in the K-th backward only and carry the
+        sum).  step() number 1 .. K - 1 of a window only advances the position; the K-th is the engine's step with grad_scale =
+        1 / (world * K).  reset_window() drops a partial window.  Not with strict_grad_scale.  1 = off: today's calls."""
         self.model, self.lr, self.grad_sync, self.pretrain_lr = model, lr, grad_sync, pretrain_lr
         self.pretrained_heads = pretrained_heads
         self.max_grad_norm = float(max_grad_norm or 0.0)
         self.weight_decay, self.warmup_steps = float(weight_decay or 0.0), int(warmup_steps or 0)
         self.lr_decay_steps = int(lr_decay_steps or 0)
         self.ema_decay, self.ema_warmup = float(ema_decay or 0.0), bool(ema_warmup)
+        self.grad_accum_steps = int(grad_accum_steps or 1)
+        if self.grad_accum_steps < 1:
+            raise ValueError("grad_accum_steps must be at least 1")
+        self._pos = 0                                     # micro-batches of the current window already taken
+        if self.grad_accum_steps > 1:
+            if getattr(model, "strict_grad_scale", False):
+                raise ValueError("strict_grad_scale cannot be combined with grad_accum_steps > 1")
+            model._micro = (0, self.grad_accum_steps)
 
     def zero_grad(self):
-        pass                      # every backward overwrites the whole flat gradient buffer
+        pass                      # every backward overwrites the whole flat gradient buffer (the engine keeps a window's sum)
+
+    def reset_window(self):
+        """Start a new accumulation window, dropping a partial one (the start of an epoch)."""
+        self._pos = 0
+        if self.grad_accum_steps > 1:
+            self.model._micro = (0, self.grad_accum_steps)
+            self.model.engine.accum_reset()
 
     def step(self):
         scale = self.grad_sync.scale if self.grad_sync is not None else 1.0
+        K = self.grad_accum_steps
+        if K > 1:
+            self._pos = (self._pos + 1) % K
+            self.model._micro = (self._pos, K)
+            if self._pos != 0:
+                return            # inside the window: the gradient is in the engine's accumulator, nothing to update yet
+            scale = scale / K
         # the engine waits for the gradient all-reduces bucket by bucket and updates each slice behind its own collective
         self.model.engine.step(self.lr, grad_scale=scale, lr_bert=self.pretrain_lr,
                                lr_news_head=self.pretrain_lr if self.pretrained_heads else None, sync=self.grad_sync,

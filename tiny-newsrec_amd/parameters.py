@@ -23,6 +23,13 @@ _STR = {"train_data_dir": "../MIND/MINDlarge_train", "test_data_dir": "../MIND/M
         "model": None, "pooling": "att", "pretrain_model_path": None, "tensorboard": None}
 
 
+def _positive_int(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be at least 1, got %s" % s)
+    return v
+
+
 def _flag_table():
     t = [("mode", str, "train", dict(choices=["train", "test", "get_teacher_emb"]))]
     t += [(kv.split("=")[0], int, int(kv.split("=")[1])) for kv in _INT.split()]
@@ -40,6 +47,7 @@ def _flag_table():
           ("ema_decay", float, 0.0, dict(help="keep an exponential moving average of the trainable parameters, ema = ema_decay * ema + (1 - ema_decay) * p after every update (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn), inside the fused update; steps skipped for an fp16 overflow do not advance it. The epoch checkpoint then also holds ema_state_dict (same keys as model_state_dict) and ema (decay, warmup, updates), and --load_ckpt_name resumes the average from it; 0 = off (the reference keeps no average)")),
           ("ema_warmup", _B, False, dict(help="with --ema_decay: use min(ema_decay, (1 + u) / (10 + u)) at the update that u updates precede (TensorFlow's ExponentialMovingAverage num_updates rule), so that a short run's average is not dominated by its starting point. The position follows the updates taken and, like the Adam moments, is not checkpointed")),
           ("use_ema", _B, False, dict(help="--mode test: evaluate the averaged parameters (the checkpoint's ema_state_dict, written by a --ema_decay run) instead of model_state_dict; an error if the checkpoint holds none")),
+          ("grad_accum_steps", _positive_int, 1, dict(help="gradient accumulation: one optimiser update per grad_accum_steps batches of --batch_size, on the mean of their gradients (summed on the device in fp32), i.e. an effective batch of grad_accum_steps * batch_size * world impressions; --warmup_steps, --lr_decay_steps and --ema_warmup count updates, not batches; under data parallelism one gradient all-reduce per update, started in the window's last backward (DistributedDataParallel's no_sync for the others); a partial window at the end of an epoch is dropped; an fp16 overflow in any of the batches skips the whole update; 1 = off (the reference updates after every batch)")),
           ("resident_tables", _B, True, dict(help="keep news_combined / teacher tables in HBM and ship indices only")),
           ("cache_frozen_layers", _B, True, dict(help="resident mode: compute the frozen lower encoder layers once per news instead of every step (identical results)")),
           ("dedup_news", _B, True, dict(help="encode each distinct news of a batch once (resident mode; identical results)")),

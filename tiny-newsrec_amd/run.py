@@ -99,7 +99,8 @@ def train(args):
                         pretrain_lr=args.pretrain_lr if (plmnr and pretrained) else None,      # PLM-NR/run.py:94-106
                         pretrained_heads=plmnr and pretrained, max_grad_norm=args.max_grad_norm,
                         weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps,
-                        ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+                        ema_decay=args.ema_decay, ema_warmup=args.ema_warmup, grad_accum_steps=args.grad_accum_steps)
+    accum_logged = False
 
     if args.synthetic:
         import synth
@@ -148,6 +149,12 @@ def train(args):
         loss_sum, acc_sum, t0 = torch.zeros((), device="cuda"), torch.zeros((), device="cuda"), time.time()
         if not args.synthetic:
             steps_cap = epoch_cap()
+        optimizer.reset_window()         # --grad_accum_steps: a window never spans two epochs
+        left_over = min(args.max_steps_per_epoch + 1, steps_cap) % args.grad_accum_steps
+        if left_over and not accum_logged:
+            accum_logged = True
+            logging.info("[{}] --grad_accum_steps {}: the last {} batch(es) of an epoch of {} fall outside a full window and "
+                         "update nothing".format(rank, args.grad_accum_steps, left_over, min(args.max_steps_per_epoch + 1, steps_cap)))
         for cnt, batch in enumerate(batches()):
             if cnt > args.max_steps_per_epoch or cnt >= steps_cap:
                 break

@@ -167,6 +167,7 @@ _SIG = {
     "tnr_grad_sumsq_parts": [_L],
     "tnr_grad_sumsq_scan": [_P, _L, _P, _P, _c.c_uint, _P],
     "tnr_grad_clip_commit": [_P, _L, _F, _F, _P, _P],
+    "tnr_grad_accum": [_P, _P, _L, _I, _P],
     "tnr_amsgrad_step_clipped": [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P, _c.c_uint, _c.c_uint, _P, _P],
     "tnr_adamw_step": [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _L, _P, _c.c_uint, _c.c_uint, _P, _P],
     "tnr_adamw_step_ema": [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _L, _P, _c.c_uint, _c.c_uint, _P,
