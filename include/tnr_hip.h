@@ -219,7 +219,11 @@ int64_t tnr_ln_bwd_blocks(int64_t M);              /* partial rows (nblk) writte
 
 /* BertSelfAttention.multi_head_attention (tnlrv3/modeling.py:205-231) for L <= 32, head size 64:
  * softmax(Q K^T / 8 + mask_add + rel) V, heads merged.  qkv (N*L, 3*A*64) bf16 = [q | k | v];
- * rel (A,32,32) fp32 from tnr_relpos_table ; ctx (N*L, A*64) bf16. */
+ * rel (A,32,32) fp32 from tnr_relpos_table ; ctx (N*L, A*64) bf16.
+ * mask_add (N,32) fp32 as tnr_embed_ln_fwd writes it.  Precondition: |q.k| / 8 + |rel| < 4400 for every (query, key) - the range
+ * in which the reference's -10000 masks at all.  Under it a key j with mask_add[n][j] - max_k mask_add[n][k] <= -9000 has
+ * probability exactly 0.0f, and the forward and backward kernels do not read its K and V rows (they may hold anything, NaN
+ * included); relative to the row's maximum, so a sequence whose keys are all padding (-10000 everywhere) keeps every key. */
 int tnr_attn_l32_fwd(const void* qkv, const float* mask_add, const float* rel, void* ctx,
                      int64_t n_seq, int L, int A, void* stream);
 /* backward: recomputes the probabilities ; dqkv (N*L, 3*A*64) bf16 ; bias_part (N, 3*A*64) fp32 (nullable) =

@@ -30,6 +30,38 @@ __device__ __forceinline__ f32x16 zero16() {
     return z;
 }
 
+__device__ __forceinline__ bf16x8 zero8() {
+    bf16x8 z;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[e] = (bf16)0.f;
+    return z;
+}
+
+// Keys the mask zeroes are not loaded (round 7).  Key j of a sequence is DEAD iff mask_add[j] - max_k mask_add[k] <= -9000: its
+// score lies at least 9000 - 2 (|q.k| / 8 + |rel|) below the row's maximum, __expf of that is exactly 0.0f, and its K and V rows
+// reach neither ctx nor any gradient (precondition |q.k| / 8 + |rel| < 4400, include/tnr_hip.h).  Relative to the row's own maximum:
+// the all-padding news (every key -10000) has no dead key and keeps its uniform softmax; keys L .. 31 carry -1e30 and are dead.
+// One wave owns one (sequence, head) and every lane holds the whole mask row in its half's mkv pieces, so the decision is one
+// in-lane maximum, one lane^32 exchange and one ballot of "my key (lane & 31) is live": bit j of the result, wave-uniform.
+// -DTNR_ATTN_LOAD_DEAD_KEYS=1 (Makefile EXTRA) restores the loads of every key for A/B builds.
+#ifndef TNR_ATTN_LOAD_DEAD_KEYS
+#define TNR_ATTN_LOAD_DEAD_KEYS 0
+#endif
+__device__ __forceinline__ uint32_t live_keys(const f32x4 (&mkv)[4], float mk_own) {
+#if TNR_ATTN_LOAD_DEAD_KEYS
+    return 0xFFFFFFFFu;
+#else
+    constexpr float DEAD_BELOW = -9000.f;
+    float mx = NEG_BIG;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) mx = fmaxf(mx, mkv[g][e]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    return (uint32_t)__ballot(!(mk_own - mx <= DEAD_BELOW));
+#endif
+}
+
 __device__ __forceinline__ bf16x8 cat4(bf16x4 a, bf16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
 
 // B-operand fragment (k = rows of the LDS tile in accumulator-permuted order, col = 32*ct + (lane&31))
@@ -60,7 +92,9 @@ __device__ __forceinline__ void acc_to_lds(char* tile, const f32x16& x, int ct, 
     }
 }
 
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ mask_add,
+// __launch_bounds__(256, 5): five waves per SIMD need <= 96 registers.  The kernel takes 91 under the bound; without it the compiler
+// spends 124 on the predicated K / V loads (four waves).  Do not drop the second argument.
+__global__ __launch_bounds__(256, 5) void attn_fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ mask_add,
                                                        const float* __restrict__ rel, bf16* __restrict__ ctx,
                                                        int64_t n_pairs, int L, int A, TnrDrop drop) {
     __shared__ __attribute__((aligned(16))) char lds[4][TB];
@@ -79,9 +113,13 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16* __restrict__ 
     // additive mask + rel-pos rows of this lane's query FIRST: they are needed right after the score MFMAs, and a load issued
     // there is a second full trip through a saturated memory pipeline (stamps: 7.7 k of a wave's 45 k cycles, tools/attn_stamps.py)
     f32x4 mkv[4], rlv[4];
+    const float* mp0 = mask_add + n * 32;
+    // this lane's key, for the live-key ballot: a fifth mask load (one dword per lane, 128 B per wave out of the line the mkv loads
+    // fetch anyway).  The value also sits in the mkv pieces of lane row or row + 32; taking it from there costs a lane exchange and a
+    // 16-way select against one more vector-memory instruction - the backward has it already (mkcol)
+    const float mkown = mp0[row];
     {
         const float* relp0 = rel + a * 1024 + row * 32;
-        const float* mp0 = mask_add + n * 32;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             mkv[g] = *(const f32x4*)(mp0 + 8 * g + 4 * h);
@@ -93,13 +131,20 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16* __restrict__ 
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         qf[s] = *(const bf16x8*)(qp + 16 * s);
-        kf[s] = *(const bf16x8*)(qp + HD + 16 * s);
+        kf[s] = zero8();
+    }
+    const uint32_t live = live_keys(mkv, mkown);
+    if ((live >> row) & 1) {                       // a dead key's K row stays zeros: its probability is 0.0f either way
+#pragma unroll
+        for (int s = 0; s < 4; ++s) kf[s] = *(const bf16x8*)(qp + HD + 16 * s);
     }
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         int idx = p * 64 + lane, r = idx >> 3, c = idx & 7;
         int rc = r < L ? r : L - 1;
-        *(bf16x8*)(my + r * TS + c * 16) = *(const bf16x8*)(qkv + (n * L + rc) * ldq + 2 * HD + a * 64 + c * 8);
+        bf16x8 vr = zero8();                       // and its V row: 0 * 0 where the loaded row gave 0 * v
+        if ((live >> r) & 1) vr = *(const bf16x8*)(qkv + (n * L + rc) * ldq + 2 * HD + a * 64 + c * 8);
+        *(bf16x8*)(my + r * TS + c * 16) = vr;
     }
     f32x16 st = zero16();
 #pragma unroll
@@ -162,8 +207,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16* __restrict
                                                        const float* __restrict__ rel, const bf16* __restrict__ dctx,
                                                        bf16* __restrict__ dqkv, float* __restrict__ bias_part,
                                                        int64_t n_pairs, int L, int A, TnrDrop drop) {
-    // per wave: K tile, dO tile, Q tile (each 4 KB, row-major [32][64]) + 256 B of row statistics
-    __shared__ __attribute__((aligned(16))) char lds[4][3 * TB + 256];
+    // per wave: K tile, dO tile, Q tile (each 4 KB, row-major [32][64]) + 256 B of row statistics + the head's rel-pos tile
+    // ([32][32] fp32, rows at pitch TS like the others): 73 KB per workgroup, two workgroups per CU
+    __shared__ __attribute__((aligned(16))) char lds[4][4 * TB + 256];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int64_t pair = (int64_t)blockIdx.x * 4 + w;
     const bool valid = pair < n_pairs;
@@ -178,33 +224,42 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16* __restrict
     char* tO = tK + TB;
     char* tQ = tK + 2 * TB;
     float* stat = (float*)(tK + 3 * TB);          // [0..31] = max + log(sum) per query, [32..63] = D per query
+    char* tR = tK + 3 * TB + 256;
 
-    // mask / rel-pos values of both orientations first (see the forward kernel): the query-row view (lane = query) and the
-    // key-column view (lane = key; 16 strided rel values) are consumed right after the two MFMA groups below
+    // The head's rel-pos tile is needed in both orientations: the query-row view (lane = query, 4 x 16 B) and the key-column view
+    // (lane = key, 16 values 128 B apart).  Fetched per lane that was 20 of the wave's 41 vector-memory instructions, 16 of them single
+    // dwords; the wave takes the 4 KB tile once, coalesced (4 x 16 B per lane), and reads both views from LDS (round 7).  These loads
+    // and the mask's go first, as in the forward kernel: what they fetch is consumed right after the two MFMA groups below.
+    f32x4 rst[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) rst[p] = *(const f32x4*)(rel + a * 1024 + (p * 64 + lane) * 4);
     f32x4 mkv[4], rlv[4];
     float relcol[16];
     const float* mp = mask_add + n * 32;
     const float mkcol = mp[row];                   // this lane's key (natural orientation)
-    {
-        const float* relp0 = rel + a * 1024 + row * 32;
-        const float* relc0 = rel + a * 1024 + row;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            mkv[g] = *(const f32x4*)(mp + 8 * g + 4 * h);
-            rlv[g] = *(const f32x4*)(relp0 + 8 * g + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) relcol[4 * g + e] = relc0[(8 * g + 4 * h + e) * 32];
-        }
-    }
+    for (int g = 0; g < 4; ++g) mkv[g] = *(const f32x4*)(mp + 8 * g + 4 * h);
     const bf16* qp = qkv + (n * L + rowc) * ldq + a * 64 + 8 * h;
     const bf16* dop = dctx + (n * L + rowc) * HD + a * 64 + 8 * h;
     bf16x8 qf[4], kf[4], vf[4], df[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         qf[s] = *(const bf16x8*)(qp + 16 * s);
-        kf[s] = *(const bf16x8*)(qp + HD + 16 * s);
-        vf[s] = *(const bf16x8*)(qp + 2 * HD + 16 * s);
         df[s] = *(const bf16x8*)(dop + 16 * s);
+        kf[s] = zero8();
+        vf[s] = zero8();
+    }
+    // a dead key's K and V rows stay zeros (see live_keys): P = dS = 0.0f there, so the tK tile, dQ, dK and dV get 0 * 0 where the
+    // loaded rows gave 0 * x; the rows of dK and dV are still stored (zeros: dqkv is a GEMM operand)
+    if ((live_keys(mkv, mkcol) >> row) & 1) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            kf[s] = *(const bf16x8*)(qp + HD + 16 * s);
+            vf[s] = *(const bf16x8*)(qp + 2 * HD + 16 * s);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
         if (row >= L) {                            // padded query rows must not contribute to dK / dV
 #pragma unroll
             for (int e = 0; e < 8; ++e) df[s][e] = (bf16)0.f;
@@ -213,6 +268,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16* __restrict
         *(bf16x8*)(tK + off) = kf[s];
         *(bf16x8*)(tO + off) = df[s];
         *(bf16x8*)(tQ + off) = qf[s];
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        int idx = p * 64 + lane, r = idx >> 3, c = idx & 7;
+        *(f32x4*)(tR + r * TS + c * 16) = rst[p];
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        rlv[g] = *(const f32x4*)(tR + row * TS + (8 * g + 4 * h) * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) relcol[4 * g + e] = *(const float*)(tR + (8 * g + 4 * h + e) * TS + row * 4);
     }
 
     // ---- transposed orientation: lanes = queries, regs = keys

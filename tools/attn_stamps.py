@@ -1,10 +1,10 @@
 """Where does a wave of the L <= 32 attention forward spend its life?  s_memtime stamps of a -DTNR_ATTN_STAMPS library copy
-(tools/_probe): t0 start, t1 = scores available (operand loads + 4 MFMAs), t2 = probabilities, t3 = P.V done, t4 = end."""
+(tools/probes/build.sh _attn -DTNR_ATTN_STAMPS -> tools/_attn; LIB=path for another copy): t0 start, t1 = scores available (operand loads + 4 MFMAs), t2 = probabilities, t3 = P.V done, t4 = end."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tiny-newsrec_amd"))
 import numpy as np, torch, tnr_hip as T
-T.LIB_PATH = os.path.join(ROOT, "tools", "_probe", "libtnr_hip.so")
+T.LIB_PATH = os.environ.get("LIB") or os.path.join(ROOT, "tools", "_attn", "libtnr_hip.so")
 dev, N, L, A, H = "cuda:0", 1760, 30, 12, 768
 td, sfx = torch.float16, "_f16"
 qkv = (torch.randn(N * L, 3 * H, device=dev) * 0.5).to(td)
