@@ -18,6 +18,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+import optstate
 import tnr_hip as T
 
 PFX = "student.news_encoder."
@@ -1678,6 +1679,64 @@ class Engine:
                 raise ValueError("%s: shape %s != %s" % (k, tuple(v.shape), shp))
             ema[o:o + n].view(shp).copy_(v.to(self.dev, torch.float32))
 
+    def optimizer_state_dict(self):
+        """Everything the fused update carries from one step to the next, as CPU data (optstate.py, format 1): Adam's moments per
+        trainable key (exp_avg / exp_avg_sq / max_exp_avg_sq = adam_m / adam_v / adam_vmax, shaped like the parameter; vmax is all
+        zeros after plain Adam), "step" = the updates TAKEN (the count the bias corrections, the schedule and ema_warmup follow),
+        the fp16 loss scaler (host fields and the four guard words), the average's update count and the dropout call counter.
+        Under fp16 the scaler is drained first, as at every epoch end, so step_count, skipped and the multiplier are final.
+        Not inside an accumulation window.  No kernel is launched (device-to-host copies only) and no device buffer changes.
+        Parameters and the average travel in state_dict() / ema_state_dict(); gradients, the accumulator, the clip and decay
+        buffers and the 16-bit copies are outputs or pure functions of the slot table.  Engines built with share= forward to the
+        owner of the flat buffers."""
+        own = self._clip_owner
+        if own is not self:
+            return own.optimizer_state_dict()
+        assert self._acc_held == 0, "optimizer_state_dict() inside an accumulation window"
+        sc, scd = self.scaler, None
+        if sc.enabled:
+            sc.drain(self)
+            scd = {f: getattr(sc, f) for f in optstate.SCALER_FIELDS}
+            scd["guard"] = [int(x) for x in sc.guard.cpu().tolist()]
+        return optstate.make(self.dtype, self.step_count, optstate.unpack(self.slot, self.adam_m, self.adam_v, self.adam_vmax), scd,
+                             None if self._ema is None else self.ema_updates, int(self.drop_calls))
+
+    def load_optimizer_state_dict(self, osd):
+        """Continue from optimizer_state_dict()'s data: call it AFTER load_state_dict() (which resets the scaler) and
+        load_ema_state_dict().  Outstanding scaler answers are consumed; adam_m / adam_v / adam_vmax are rewritten whole (zero
+        between the slots); then the scaler's host fields and guard words (guard[1] and scaler.skipped agree: the kernels compute
+        guard[1] - known_skips), step_count, the average's update count (its setter reads scaler.skipped) and the dropout call
+        counter, in that order.  Parameters, 16-bit copies, the average's buffer, flat_g and the accumulator are not touched, and
+        no kernel is launched (host-to-device copies only).  ValueError: unknown format, a state saved under the other 16-bit
+        type, a shape that differs; KeyError: a trainable key that is missing, a key that is not trainable here.  Nothing is
+        written before those checks have passed."""
+        own = self._clip_owner
+        if own is not self:
+            return own.load_optimizer_state_dict(osd)
+        assert self._acc_held == 0, "load_optimizer_state_dict() inside an accumulation window"
+        optstate.check_header(osd, self.dtype)
+        m, v, vmax = optstate.pack(self.slot, self.n_train, osd["state"])
+        sc = self.scaler
+        if sc.enabled:
+            saved = osd.get("scaler")
+            if saved is None:
+                raise ValueError("optimiser state: no scaler state, but this engine runs fp16 with the dynamic loss scale")
+            if int(saved["guard"][1]) != int(saved["skipped"]):
+                raise ValueError("optimiser state: guard[1] = %d but skipped = %d (the state was not saved drained)"
+                                 % (int(saved["guard"][1]), int(saved["skipped"])))
+            sc.drain(self)
+        self.adam_m.copy_(m)
+        self.adam_v.copy_(v)
+        self.adam_vmax.copy_(vmax)
+        if sc.enabled:
+            sc.mult, sc.clean, sc.run_of_skips = float(saved["mult"]), int(saved["clean"]), int(saved["run_of_skips"])
+            sc.skipped, sc.stamp = int(saved["skipped"]), int(saved["stamp"])
+            sc.guard.copy_(torch.tensor([int(x) for x in saved["guard"]], dtype=torch.int32))
+        self.step_count = int(osd["step"])
+        if osd.get("ema_updates") is not None:
+            self.ema_updates = int(osd["ema_updates"])
+        self.drop_calls = int(osd["dropout_calls"])
+
     def step(self, lr, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, lr_bert=None, amsgrad=True, lr_news_head=None, sync=None,
              max_grad_norm=None, weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=None, ema_warmup=False):
         """torch.optim.Adam(amsgrad=True).step() (run.py:134,195) + refresh of the 16-bit weight copies.
@@ -1702,8 +1761,8 @@ class Engine:
         warmup_steps = W, lr_decay_steps = T: every rate is multiplied by lr_schedule(u, W, T), u = the number of updates TAKEN
         before this one, from the step_count the bias corrections use: under fp16 the kernel gets the rates of u, u - 1, u - 2
         beside the three bias corrections and picks by the skips the host has not accounted for, so a skipped step advances
-        neither Adam's count nor the schedule and decays nothing.  The position is optimiser state (not checkpointed, like m, v,
-        vmax).  With any of the three on, every range / bucket launch goes through tnr_adamw_step (clip and guard as before);
+        neither Adam's count nor the schedule and decays nothing.  The position is optimiser state: optimizer_state_dict() saves
+        it as "step" beside m, v and vmax (run.py --save_optimizer True / --resume True).  With any of the three on, every range / bucket launch goes through tnr_adamw_step (clip and guard as before);
         all off (None, 0): the calls, kernels, bits and buffers of a step without them.
         ema_decay = d in (0, 1]: an exponential moving average of the trainable parameters, ema <- d ema + (1 - d) p_new inside the
         update kernel (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(d)), in an fp32 buffer laid out like flat[True]

@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 import engine as E
+import optstate
 
 
 def read_model_config(path, synthetic=False):
@@ -255,6 +256,18 @@ class Model(_Shell):
         """The average resumes from a checkpoint's ema_state_dict (this model's keys); the parameters are not touched."""
         self.engine.load_ema_state_dict({self._engine_key(k): v for k, v in sd.items()})
 
+    def optimizer_state_dict(self):
+        """Engine.optimizer_state_dict() with "state" under this model's own keys (the mapping of ema_state_dict: a PLM-NR
+        checkpoint's optimiser state is keyed like its model_state_dict)."""
+        mine = {self._engine_key(k): k for k in self.state_dict()}
+        return optstate.rekey(self.engine.optimizer_state_dict(), lambda k: mine[k])
+
+    def load_optimizer_state_dict(self, osd):
+        """The optimiser resumes from a checkpoint's optimizer_state_dict (this model's keys); call it after load_state_dict()
+        and load_ema_state_dict().  The parameters and the average are not touched."""
+        optstate.check_header(osd, self.engine.dtype)
+        self.engine.load_optimizer_state_dict(optstate.rekey(osd, self._engine_key))
+
     def forward(self, history, history_mask, candidate, label, teacher_history_embs, teacher_candidate_embs):
         eng = self.engine
         if isinstance(history, tuple) and len(history) == 4:      # resident-mode IndexBatch
@@ -387,6 +400,22 @@ class TnrAdam:
         if self.grad_accum_steps > 1:
             self.model._micro = (0, self.grad_accum_steps)
             self.model.engine.accum_reset()
+
+    def state_dict(self):
+        """torch.optim.Optimizer.state_dict's counterpart: the model's optimizer_state_dict() (moments, updates taken, fp16 loss
+        scaler, the average's count, dropout calls).  Not inside an accumulation window."""
+        if self._pos != 0:
+            raise RuntimeError("TnrAdam.state_dict() inside an accumulation window (%d of %d micro-batches taken)"
+                               % (self._pos, self.grad_accum_steps))
+        return self.model.optimizer_state_dict()
+
+    def load_state_dict(self, osd):
+        """Resume from state_dict()'s data, after the model's load_state_dict() / load_ema_state_dict(); a new window starts."""
+        if self._pos != 0:
+            raise RuntimeError("TnrAdam.load_state_dict() inside an accumulation window (%d of %d micro-batches taken)"
+                               % (self._pos, self.grad_accum_steps))
+        self.model.load_optimizer_state_dict(osd)
+        self.reset_window()
 
     def step(self):
         scale = self.grad_sync.scale if self.grad_sync is not None else 1.0

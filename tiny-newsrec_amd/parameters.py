@@ -42,12 +42,14 @@ def _flag_table():
           ("train_embeddings", _B, False, dict(help="also fine-tune bert.embeddings.* (word / position / token-type tables and the embedding LayerNorm) at the encoder's learning rate; the reference freezes them (run.py:101-112); needs --bert_trainable_layer")),
           ("max_grad_norm", float, 0.0, dict(help="clip the gradient by its global L2 norm, torch.nn.utils.clip_grad_norm_ semantics (one norm over everything trainable, coef = min(1, max_norm / (norm + 1e-6))), done on the device after the gradient all-reduce; 0 = off (the reference does not clip)")),
           ("weight_decay", float, 0.0, dict(help="decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * weight_decay before the Adam / AMSGrad update) of the 2-D weights outside LayerNorm - biases, LayerNorm parameters and pad_doc are exempt; with --train_embeddings the embedding tables decay - inside the fused update; 0 = off (the reference uses Adam without decay)")),
-          ("warmup_steps", int, 0, dict(help="multiply every learning rate by u / warmup_steps over the first warmup_steps updates (u = updates taken so far: the first update has rate 0; steps skipped for an fp16 overflow do not count); 0 = no warmup (the reference's rate is constant). The schedule's position is optimiser state and, like the Adam moments, is not checkpointed")),
-          ("lr_decay_steps", int, 0, dict(help="after the warmup, decay every learning rate linearly to 0 at update lr_decay_steps (transformers' get_linear_schedule_with_warmup with num_training_steps = lr_decay_steps), 0 from there on; 0 = constant after the warmup (the reference's rate is constant). Not checkpointed, like the Adam moments")),
+          ("warmup_steps", int, 0, dict(help="multiply every learning rate by u / warmup_steps over the first warmup_steps updates (u = updates taken so far: the first update has rate 0; steps skipped for an fp16 overflow do not count); 0 = no warmup (the reference's rate is constant). The schedule's position is optimiser state: --save_optimizer True writes it into the epoch checkpoint with the Adam moments, and --resume True continues from it (without them a restarted run ramps again from rate 0)")),
+          ("lr_decay_steps", int, 0, dict(help="after the warmup, decay every learning rate linearly to 0 at update lr_decay_steps (transformers' get_linear_schedule_with_warmup with num_training_steps = lr_decay_steps), 0 from there on; 0 = constant after the warmup (the reference's rate is constant). The position is saved by --save_optimizer True and restored by --resume True, like the Adam moments")),
           ("ema_decay", float, 0.0, dict(help="keep an exponential moving average of the trainable parameters, ema = ema_decay * ema + (1 - ema_decay) * p after every update (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn), inside the fused update; steps skipped for an fp16 overflow do not advance it. The epoch checkpoint then also holds ema_state_dict (same keys as model_state_dict) and ema (decay, warmup, updates), and --load_ckpt_name resumes the average from it; 0 = off (the reference keeps no average)")),
-          ("ema_warmup", _B, False, dict(help="with --ema_decay: use min(ema_decay, (1 + u) / (10 + u)) at the update that u updates precede (TensorFlow's ExponentialMovingAverage num_updates rule), so that a short run's average is not dominated by its starting point. The position follows the updates taken and, like the Adam moments, is not checkpointed")),
+          ("ema_warmup", _B, False, dict(help="with --ema_decay: use min(ema_decay, (1 + u) / (10 + u)) at the update that u updates precede (TensorFlow's ExponentialMovingAverage num_updates rule), so that a short run's average is not dominated by its starting point. The position follows the updates taken; --save_optimizer True saves it and --resume True restores it, like the Adam moments")),
           ("use_ema", _B, False, dict(help="--mode test: evaluate the averaged parameters (the checkpoint's ema_state_dict, written by a --ema_decay run) instead of model_state_dict; an error if the checkpoint holds none")),
           ("grad_accum_steps", _positive_int, 1, dict(help="gradient accumulation: one optimiser update per grad_accum_steps batches of --batch_size, on the mean of their gradients (summed on the device in fp32), i.e. an effective batch of grad_accum_steps * batch_size * world impressions; --warmup_steps, --lr_decay_steps and --ema_warmup count updates, not batches; under data parallelism one gradient all-reduce per update, started in the window's last backward (DistributedDataParallel's no_sync for the others); a partial window at the end of an epoch is dropped; an fp16 overflow in any of the batches skips the whole update; 1 = off (the reference updates after every batch)")),
+          ("save_optimizer", _B, False, dict(help="the epoch checkpoint also holds optimizer_state_dict (Adam's moments per trainable key, the updates taken - the position of --warmup_steps / --lr_decay_steps / --ema_warmup -, the fp16 loss scaler, the average's update count, the dropout call counter: 12 bytes per trainable element) and train_state (epoch, updates, the flags it ran with); off = the reference's checkpoint keys")),
+          ("resume", _B, False, dict(help="with --load_ckpt_name: continue the run that wrote that checkpoint with --save_optimizer True - the optimiser state is restored after the parameters (and the average), the epoch loop and the file-fed loader's shard / shuffle seeds go on at the saved epoch - bit for bit what the uninterrupted run computes; flags that differ from the saved ones are logged as a warning. Off, --load_ckpt_name restores the parameters (and the average) only and --start_epoch is what it was")),
           ("resident_tables", _B, True, dict(help="keep news_combined / teacher tables in HBM and ship indices only")),
           ("cache_frozen_layers", _B, True, dict(help="resident mode: compute the frozen lower encoder layers once per news instead of every step (identical results)")),
           ("dedup_news", _B, True, dict(help="encode each distinct news of a batch once (resident mode; identical results)")),
@@ -71,8 +73,15 @@ def build_parser():
     return ap
 
 
+def check_args(args):
+    """Flag combinations that cannot run, refused before anything is built."""
+    if getattr(args, "resume", False) and not getattr(args, "load_ckpt_name", None):
+        raise ValueError("--resume True needs --load_ckpt_name (the checkpoint a --save_optimizer True run wrote)")
+
+
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
+    check_args(args)
     logging.info(args)
     return args
 

@@ -33,7 +33,18 @@ def _load_inputs(args):
     return news_index, np.concatenate([title, mask], axis=-1), tables, cat, sub
 
 
+def _train_flags(args, world):
+    """The flags a --save_optimizer checkpoint records (train_state["flags"]): what a --resume run compares its own against."""
+    names = ("lr", "pretrain_lr", "weight_decay", "warmup_steps", "lr_decay_steps", "ema_decay", "ema_warmup", "grad_accum_steps",
+             "max_grad_norm", "batch_size", "dtype")
+    flags = {k: getattr(args, k) for k in names}
+    flags["world"] = world
+    return flags
+
+
 def train(args):
+    if getattr(args, "resume", False) and not args.load_ckpt_name:          # (parse_args refuses it too; args may come from elsewhere)
+        raise ValueError("--resume True needs --load_ckpt_name (the checkpoint a --save_optimizer True run wrote)")
     import dist
     from dataloader import DataLoaderTrain, IndexBatch
     from model_bert import Model, ModelBert, TnrAdam
@@ -82,6 +93,7 @@ def train(args):
                 if k.startswith("student"):
                     sd[k] = v
     model.load_state_dict(sd)
+    loaded = None
     if args.load_ckpt_name is not None:                                      # run.py:125-129
         ck = utils.get_checkpoint(args.model_dir, args.load_ckpt_name)
         loaded = torch.load(ck, map_location="cpu")
@@ -101,6 +113,27 @@ def train(args):
                         weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps,
                         ema_decay=args.ema_decay, ema_warmup=args.ema_warmup, grad_accum_steps=args.grad_accum_steps)
     accum_logged = False
+    first_epoch = args.start_epoch
+    if args.resume:
+        # the run that wrote the checkpoint goes on: optimiser state behind the parameters and the average (above), then the epoch
+        if "optimizer_state_dict" not in loaded:
+            raise KeyError(f"--resume True: {ck} holds no optimizer_state_dict (it was not written with --save_optimizer True)")
+        optimizer.load_state_dict(loaded["optimizer_state_dict"])
+        # every rank read the same file; one source for the buffers all the same (hvd.broadcast_optimizer_state, run.py:143)
+        dist.broadcast_flat([eng.adam_m, eng.adam_v, eng.adam_vmax] + ([eng._ema] if eng._ema is not None else []))
+        ts = loaded["train_state"]
+        first_epoch = int(ts["epoch"])
+        if args.start_epoch not in (0, first_epoch):
+            raise ValueError(f"--resume True: {ck} was written at the end of epoch {first_epoch}, --start_epoch says {args.start_epoch}")
+        mine = _train_flags(args, size)
+        for k, v in ts.get("flags", {}).items():
+            if k in mine and mine[k] != v:
+                logging.warning(f"--resume True: --{k} is {mine[k]}, the run that wrote {ck} had {v}" if k != "world" else
+                                f"--resume True: {size} worker(s), the run that wrote {ck} had {v}")
+        logging.info(f"[{rank}] Resumed from {ck}: {eng.step_count} updates taken, continuing at epoch {first_epoch}")
+        if args.epochs <= first_epoch:
+            logging.info(f"[{rank}] --epochs {args.epochs} is not beyond the saved epoch {first_epoch}: nothing left to train")
+            return
 
     if args.synthetic:
         import synth
@@ -131,6 +164,8 @@ def train(args):
                                  enable_gpu=True, resident=args.resident_tables)
         dev_news, dev_tab = getattr(loader, "dev_news", None), loader.dev_tables
         batches = lambda: iter(loader)
+        if args.resume:
+            loader.epoch = first_epoch - 1       # shard assignment and shuffle seeds go on as in the uninterrupted run
 
         def epoch_cap():
             # uneven shards: every rank runs the step count the shortest shard of THIS epoch allows (the loader re-shards the
@@ -145,7 +180,7 @@ def train(args):
         logging.info("[%d] frozen layers 0..%d cached for %d news (%.2f GB)" % (
             rank, eng.lo - 1, dev_news.shape[0], eng.fcache[0].numel() * 4 / 1e9))
     logging.info("Training...")
-    for ep in range(args.start_epoch, args.epochs):
+    for ep in range(first_epoch, args.epochs):
         loss_sum, acc_sum, t0 = torch.zeros((), device="cuda"), torch.zeros((), device="cuda"), time.time()
         if not args.synthetic:
             steps_cap = epoch_cap()
@@ -198,6 +233,10 @@ def train(args):
             if esd is not None:          # --ema_decay: the averaged model beside the trained one, which stays what the reference loads
                 ckpt["ema_state_dict"] = {k: v.cpu() for k, v in esd.items()}
                 ckpt["ema"] = {"decay": args.ema_decay, "warmup": bool(args.ema_warmup), "updates": eng.ema_updates}
+            if args.save_optimizer:      # what --resume True continues from (after the drain above: the counts are final)
+                optimizer.reset_window()     # a partial window at the end of the epoch is dropped, as the next epoch's start drops it
+                ckpt["optimizer_state_dict"] = optimizer.state_dict()
+                ckpt["train_state"] = {"epoch": ep + 1, "updates": eng.step_count, "flags": _train_flags(args, size)}
             torch.save(ckpt, ckpt_path)
             logging.info(f"Model saved to {ckpt_path}")
     if not args.synthetic:

@@ -83,6 +83,22 @@ class Stage1Engine:
     def ema_updates(self):
         return self.title.ema_updates
 
+    def optimizer_state_dict(self):
+        """Engine.optimizer_state_dict of the title engine, which owns the shared buffers, the step count and the scaler;
+        "dropout_calls" is the pair [title, body]: each pass numbers its own forward calls (set_dropout)."""
+        osd = self.title.optimizer_state_dict()
+        osd["dropout_calls"] = [int(self.title.drop_calls), int(self.body.drop_calls)]
+        return osd
+
+    def load_optimizer_state_dict(self, osd):
+        """After load_state_dict() / load_ema_state_dict(): Engine.load_optimizer_state_dict on the title engine, then both
+        passes' dropout call counters."""
+        calls = osd["dropout_calls"]
+        if not isinstance(calls, (list, tuple)) or len(calls) != 2:
+            raise ValueError("optimiser state: dropout_calls must be the pair [title, body] for a Stage1Engine, got %r" % (calls,))
+        self.title.load_optimizer_state_dict(dict(osd, dropout_calls=int(calls[0])))
+        self.body.drop_calls = int(calls[1])
+
     def grad(self, name):
         return self.title.grad(name)
 
