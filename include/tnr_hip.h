@@ -682,6 +682,27 @@ int tnr_attn_long_bwd_do_f16(const void* qkv, const float* mask_add, const float
                          const tnr_dropout_t* drop, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * Top-K retrieval (csrc/retrieve.hip): of all Nn news, the K each user should see.  The reference stops at per-impression dot
+ * products on the host (Tiny-NewsRec/run.py:254-262); this is the serving step the student exists for.
+ *   s(u, n) = sum_k users[u, k] * news[n, k], an fp32 fma chain on the exact fp32 MFMA whose k order depends on D alone: a
+ *   (user row, news row) pair has the same score bits in every call, tile, split and launch position.
+ * Row n is eligible for user u when first_row <= n < Nn, n is not among excl[u, 0:E] (excl may be NULL with E = 0; entries outside
+ * [first_row, Nn) are ignored, duplicates allowed) and s(u, n) is not NaN.  a is before b iff s_a > s_b, or s_a == s_b and
+ * n_a < n_b.  Row u of out_idx / out_score (each (Nu, K), dense) is the first K eligible rows in that order with the kernel's own
+ * score bits; slots beyond the eligible rows hold idx -1, score -inf.
+ * The news range is cut into `splits` contiguous parts (0 = the library chooses from Nu, Nn and the CU count; never more parts
+ * than 8192 / K, 1024, or tiles of 128 rows): one workgroup per (user tile, part) writes a partial list into `work`, a second
+ * launch merges them (skipped for one part).  The outputs are bit-identical for every `splits`.  No float atomics.
+ * Limits: 1 <= K <= 128, D % 4 == 0, 4 <= D <= 1024, E <= 512, Nn < 2^31, strides >= D / >= E (16-byte aligned operands with
+ * strides % 4 == 0 take 16-byte loads, others scalar ones).  Anything else, a null pointer or work_bytes below
+ * tnr_topk_workspace launches nothing and returns TNR_EINVAL.  tnr_topk_workspace: bytes, host arithmetic only (no device
+ * is asked: it plans splits = 0 for 256 CUs); 0 for a bad request. */
+int64_t tnr_topk_workspace(int64_t Nu, int64_t Nn, int K, int splits);
+int tnr_topk_scores(const float* users, int64_t u_rs, int64_t Nu, const float* news, int64_t n_rs, int64_t Nn, int64_t first_row,
+                    int D, const int32_t* excl, int64_t e_rs, int E, int K, int32_t* out_idx, float* out_score, int splits,
+                    void* work, int64_t work_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Collectives of the data-parallel step.  Replace hvd.init / hvd.broadcast_parameters /
  * hvd.broadcast_optimizer_state (Tiny-NewsRec/run.py:141-144, utils.py:43-60) and the gradient all-reduce inside
  * hvd.DistributedOptimizer (run.py:145-149: average of the trainable parameters' gradients, fp32, no compression).

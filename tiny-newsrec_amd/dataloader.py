@@ -322,3 +322,13 @@ class DataLoaderTest(DataLoaderTrain):
         if self.enable_gpu:
             h, m = h.cuda(), m.cuda()
         return h, m, C, Y
+
+
+class DataLoaderRecommend(DataLoaderTest):
+    """--mode recommend: DataLoaderTest's batches plus each line's impression id and user id (the first two columns), for the
+    output file -> (hist_idx, mask, [cand_idx arrays], [label arrays], [impression ids], [user ids])."""
+
+    def _process(self, batch):
+        h, m, C, Y = super()._process(batch)
+        heads = [raw.decode("utf-8").split("\t", 2)[:2] for raw in batch]
+        return h, m, C, Y, [x[0] for x in heads], [x[1] for x in heads]

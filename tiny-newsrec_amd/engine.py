@@ -351,6 +351,7 @@ class Engine:
         self.scaler = share.scaler if share is not None else LossScaler(self.dev, self.f16)
         self.step_count = 0
         self._n_alloc = 0
+        self._topk_ws = {}           # topk's workspace, by size: allocated by the first call, never by training
         if share is None:
             self._build_params()
             self._build_shadows()
@@ -1041,6 +1042,44 @@ class Engine:
         self._user_forward(rows, B * U, 1, self._user_params(ue, 1), hidx, hidx, mask, self.epre_u, self.dS, B * D, self.score,
                            self.e_u, self.alpha_u, self.den_u, B, 0, self.nr_s)
         return self.dS[:B].clone()
+
+    @torch.no_grad()
+    def topk(self, users, news_scoring, k, exclude=None, first_row=1, splits=0):
+        """Of all rows of news_scoring (Nn, D), the k each user should see (tnr_topk_scores, include/tnr_hip.h): scores on the
+        exact fp32 MFMA, selection fused behind them, the (Nu, Nn) score matrix never exists.  users: any fp32 (Nu, D) device
+        tensor; exclude: int32 (Nu, E) rows never to return (ids < first_row, e.g. the padding 0, are ignored).
+        -> (idx int32 (Nu, k), score fp32 (Nu, k)), best first, ties to the lower row, idx -1 / score -inf where fewer than k
+        rows are eligible.  The workspace is a torch allocation of the size the library states, cached by size."""
+        assert users.dtype == torch.float32 and news_scoring.dtype == torch.float32 and users.dim() == 2 and news_scoring.dim() == 2
+        assert users.shape[1] == news_scoring.shape[1] and users.stride(1) == 1 and news_scoring.stride(1) == 1
+        Nu, D = users.shape
+        Nn = news_scoring.shape[0]
+        e_rs = E = 0
+        if exclude is not None:
+            assert exclude.shape[0] == Nu and exclude.dim() == 2
+            exclude = exclude.to(device=users.device, dtype=torch.int32)
+            if exclude.stride(1) != 1:
+                exclude = exclude.contiguous()
+            e_rs, E = exclude.stride(0), exclude.shape[1]
+        idx = torch.empty((Nu, k), device=users.device, dtype=torch.int32)
+        score = torch.empty((Nu, k), device=users.device, dtype=torch.float32)
+        nbytes = int(T.query("tnr_topk_workspace", Nu, Nn, k, splits))
+        cache = self._topk_ws
+        work = cache.get(nbytes)
+        if work is None:
+            cache.clear()                                          # one size at a time: serving batches repeat their shape
+            work = cache[nbytes] = torch.empty((max(nbytes, 8),), device=users.device, dtype=torch.uint8)
+        T.call("tnr_topk_scores", users, users.stride(0), Nu, news_scoring, news_scoring.stride(0), Nn, first_row, D,
+               exclude if E else None, e_rs, E, k, idx, score, splits, work, nbytes)
+        return idx, score
+
+    @torch.no_grad()
+    def recommend(self, news_scoring, hist_idx, history_mask, k, exclude_history=True):
+        """user_vectors(...) followed by topk over the whole table (row 0, the padding news, is never returned): the serving
+        step.  exclude_history: the user's clicked rows are not recommended again (hist_idx's padding zeros match nothing).
+        B <= the engine's batch; every buffer and counter is left as user_vectors leaves it."""
+        users = self.user_vectors(news_scoring, hist_idx, history_mask)
+        return self.topk(users, news_scoring, k, exclude=hist_idx if exclude_history else None, first_row=1)
 
     def _prepare(self, B):
         # buffers are sized for the exact batch: row strides of the stacked (T, Rt, D) arrays and the

@@ -31,7 +31,7 @@ def _positive_int(s):
 
 
 def _flag_table():
-    t = [("mode", str, "train", dict(choices=["train", "test", "get_teacher_emb"]))]
+    t = [("mode", str, "train", dict(choices=["train", "test", "get_teacher_emb", "recommend"]))]
     t += [(kv.split("=")[0], int, int(kv.split("=")[1])) for kv in _INT.split()]
     t += [(kv.split("=")[0], float, float(kv.split("=")[1])) for kv in _FLOAT.split()]
     t += [(kv.split("=")[0], _B, kv.split("=")[1] == "1") for kv in _BOOL.split()]     # enable_hvd: True = data parallel over RCCL
@@ -47,6 +47,9 @@ def _flag_table():
           ("ema_decay", float, 0.0, dict(help="keep an exponential moving average of the trainable parameters, ema = ema_decay * ema + (1 - ema_decay) * p after every update (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn), inside the fused update; steps skipped for an fp16 overflow do not advance it. The epoch checkpoint then also holds ema_state_dict (same keys as model_state_dict) and ema (decay, warmup, updates), and --load_ckpt_name resumes the average from it; 0 = off (the reference keeps no average)")),
           ("ema_warmup", _B, False, dict(help="with --ema_decay: use min(ema_decay, (1 + u) / (10 + u)) at the update that u updates precede (TensorFlow's ExponentialMovingAverage num_updates rule), so that a short run's average is not dominated by its starting point. The position follows the updates taken; --save_optimizer True saves it and --resume True restores it, like the Adam moments")),
           ("use_ema", _B, False, dict(help="--mode test: evaluate the averaged parameters (the checkpoint's ema_state_dict, written by a --ema_decay run) instead of model_state_dict; an error if the checkpoint holds none")),
+          ("top_k", _positive_int, 10, dict(help="--mode recommend: news per user, 1..128 (the fused score-and-select kernel's limit)")),
+          ("recommend_out", str, None, dict(help="--mode recommend: the output file, one line per behaviours line in file order, `impression_id \\t user_id \\t nid:score nid:score ...` best first; with more than one rank, rank r writes PATH.r for its shard; default <model_dir>/recommend.tsv")),
+          ("exclude_history", _B, True, dict(help="--mode recommend: never recommend a news the user's history already holds")),
           ("grad_accum_steps", _positive_int, 1, dict(help="gradient accumulation: one optimiser update per grad_accum_steps batches of --batch_size, on the mean of their gradients (summed on the device in fp32), i.e. an effective batch of grad_accum_steps * batch_size * world impressions; --warmup_steps, --lr_decay_steps and --ema_warmup count updates, not batches; under data parallelism one gradient all-reduce per update, started in the window's last backward (DistributedDataParallel's no_sync for the others); a partial window at the end of an epoch is dropped; an fp16 overflow in any of the batches skips the whole update; 1 = off (the reference updates after every batch)")),
           ("save_optimizer", _B, False, dict(help="the epoch checkpoint also holds optimizer_state_dict (Adam's moments per trainable key, the updates taken - the position of --warmup_steps / --lr_decay_steps / --ema_warmup -, the fp16 loss scaler, the average's update count, the dropout call counter: 12 bytes per trainable element) and train_state (epoch, updates, the flags it ran with); off = the reference's checkpoint keys")),
           ("resume", _B, False, dict(help="with --load_ckpt_name: continue the run that wrote that checkpoint with --save_optimizer True - the optimiser state is restored after the parameters (and the average), the epoch loop and the file-fed loader's shard / shuffle seeds go on at the saved epoch - bit for bit what the uninterrupted run computes; flags that differ from the saved ones are logged as a warning. Off, --load_ckpt_name restores the parameters (and the average) only and --start_epoch is what it was")),

@@ -341,9 +341,57 @@ def test(args, collect=None):
     return sums, n_local, cnt_metric
 
 
+def recommend(args):
+    """--mode recommend: of ALL news of --test_data_dir, the --top_k each behaviours line's user should see (the serving step the
+    reference stops short of: its test mode scores only the candidates an impression lists).  The checkpoint is loaded as test()
+    loads it; one line per behaviours line, in file order: impression_id \\t user_id \\t nid:score ... best first."""
+    from dataloader import DataLoaderRecommend
+    size, rank, local = utils.init_hvd_cuda(args.enable_hvd, args.enable_gpu)
+    ckpt_path = utils.get_checkpoint(args.model_dir, args.load_ckpt_name) if args.load_ckpt_name else utils.latest_checkpoint(args.model_dir)
+    assert ckpt_path is not None, "No ckpt found"
+    ckpt = torch.load(ckpt_path, map_location="cpu")
+    if getattr(args, "use_ema", False):
+        if "ema_state_dict" not in ckpt:
+            raise KeyError(f"--use_ema True: {ckpt_path} holds no ema_state_dict (it was not trained with --ema_decay)")
+        sd = ckpt["ema_state_dict"]
+    else:
+        sd = ckpt["model_state_dict"]
+    eng = _forward_engine(args, args.num_student_layers, sd)
+    logging.info(f"Model loaded from {ckpt_path}" + (" (the EMA of the weights)" if getattr(args, "use_ema", False) else ""))
+    news_index, news_combined = _news_table(args, args.test_data_dir, "test")
+    news_scoring = eng.encode_news(torch.from_numpy(news_combined).cuda())
+    logging.info("news scoring num: {}".format(news_scoring.shape[0]))
+    nid_of = [None] * news_scoring.shape[0]                      # row -> the table's string id (row 0 is the padding news)
+    for nid, row in news_index.items():
+        nid_of[row] = nid
+    k = args.top_k
+    out_path = args.recommend_out or os.path.join(args.model_dir, "recommend.tsv")
+    if size > 1:
+        out_path = "%s.%d" % (out_path, rank)
+    loader = DataLoaderRecommend(news_index=news_index, data_dir=args.test_data_dir, filename_pat=args.filename_pat, args=args,
+                                 world_size=size, worker_rank=rank, cuda_device_idx=local, enable_prefetch=True,
+                                 enable_shuffle=False, enable_gpu=True)
+    n_local, t0 = 0, time.time()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        for cnt, (h, m, _, _, iids, uids) in enumerate(loader):
+            idx, score = eng.recommend(news_scoring, h, m, k, exclude_history=args.exclude_history)
+            idx, score = idx.cpu().numpy(), score.cpu().numpy()
+            for iid, uid, ii, ss in zip(iids, uids, idx, score):
+                f.write("%s\t%s\t%s\n" % (iid, uid, " ".join("%s:%.6g" % (nid_of[i], s) for i, s in zip(ii, ss) if i >= 0)))
+            n_local += h.shape[0]
+            if cnt % args.log_steps == 0:
+                logging.info("[{}] Ed: {}: top-{} of {} news, {:.1f} users/s".format(rank, n_local, k, news_scoring.shape[0] - 1,
+                                                                                   n_local / max(time.time() - t0, 1e-9)))
+    loader.join()
+    logging.info("[{}] local_sample_num: {}, {:.1f} users/s, written to {}".format(rank, n_local, n_local / max(time.time() - t0, 1e-9),
+                                                                                 out_path))
+    return out_path, n_local
+
+
 if __name__ == "__main__":
     utils.setuplogger()
     args = parse_args()
-    {"train": train, "test": test, "get_teacher_emb": get_teacher_emb}[args.mode](args)
+    {"train": train, "test": test, "get_teacher_emb": get_teacher_emb, "recommend": recommend}[args.mode](args)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

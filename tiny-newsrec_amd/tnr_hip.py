@@ -175,6 +175,8 @@ _SIG = {
     "tnr_refresh_shadows": [_P, _I, _L, _P, _P],
     "tnr_cast_f32_to_bf16": [_P, _P, _L, _P],
     "tnr_cast_bf16_to_f32": [_P, _P, _L, _P],
+    "tnr_topk_workspace": [_L, _L, _I, _I],
+    "tnr_topk_scores": [_P, _L, _L, _P, _L, _L, _L, _I, _P, _L, _I, _I, _P, _P, _I, _P, _L, _P],
 }
 # entry points that exist twice: bf16 (plain name) and fp16 (suffix _f16)
 TYPED = ["tnr_embed_ln_fwd", "tnr_embed_ln_fwd_indexed", "tnr_embed_ln_bwd", "tnr_embed_ln_bwd_indexed", "tnr_gemm_nt", "tnr_gemm_nt_ex", "tnr_gemm_colsum_rows", "tnr_gemm_nt_route",
@@ -194,7 +196,7 @@ TYPED += ["tnr_gemm_nt_do", "tnr_ln_bwd_do", "tnr_gemm_nt_do_split", "tnr_ln_bwd
 for _n in TYPED:
     _SIG[_n + "_f16"] = _SIG[_n]
 _RET = {"tnr_attpool_long_ws_elems": _L, "tnr_attpool_long_ws_elems_f16": _L, "tnr_gemm_tn_ws_elems": _L, "tnr_gemm_tn_ws_elems_f16": _L, "tnr_gemm_colsum_rows_f16": _L, "tnr_gemm_colsum_rows": _L, "tnr_ln_bwd_part_elems": _L, "tnr_ln_bwd_blocks": _L, "tnr_embed_ln_bwd_part_elems": _L, "tnr_embed_ln_bwd_blocks": _L, "tnr_colsum_part_elems": _L,
-        "tnr_user_bwd_part_stride": _L, "tnr_grad_sumsq_parts": _L}
+        "tnr_user_bwd_part_stride": _L, "tnr_grad_sumsq_parts": _L, "tnr_topk_workspace": _L}
 EXPORTS = sorted(_SIG) + ["tnr_last_error"]
 
 _lib = None
