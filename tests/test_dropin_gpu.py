@@ -321,35 +321,15 @@ def test_run_py_train_from_mind_format_files(tmp_path):
     """`python run.py --mode train` on real-format inputs (news.tsv through the BERT wordpiece tokenizer, behaviors_np4_*.tsv
     shards through the TF-free streamer, teacher-embedding pickles, PLM-NR teacher checkpoints): the demo.sh train flow
     end to end, resident tables + in-batch de-duplication on, one epoch, checkpoint written in the reference's layout."""
-    import pickle
-    import hashinit
-    from helpers import FULL, state_shapes
+    from filefed_data import run_py_inputs
     data = os.path.join(GOLDEN, "data")
-    words = sorted({w for ln in open(os.path.join(data, "news.tsv")) for w in ln.split("\t")[3].lower().split()})
-    vocab = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"] + words
-    (tmp_path / "vocab.txt").write_text("\n".join(vocab) + "\n")
-    (tmp_path / "config.json").write_text(json.dumps(dict(
-        hidden_size=768, num_attention_heads=12, intermediate_size=3072, vocab_size=len(vocab), max_position_embeddings=64,
-        type_vocab_size=2, layer_norm_eps=1e-12)))
-    n_news = sum(1 for _ in open(os.path.join(data, "news.tsv")))
-    embs, ckpts = [], []
-    for i in range(2):
-        p = tmp_path / ("teacher_emb_%d.pkl" % i)
-        with open(p, "wb") as f:
-            pickle.dump(hashinit.hash_normal(50 + i, "temb", (n_news + 1, 256)), f)
-        embs.append(str(p))
-        sd = hashinit.init_state_dict(60 + i, {k[len("student."):]: v for k, v in state_shapes(FULL, 1, 256, 0).items()
-                                               if k.startswith("student.user_encoder.")})
-        ck = tmp_path / ("teacher_%d.pt" % i)
-        torch.save({"model_state_dict": {k: torch.from_numpy(v) for k, v in sd.items()}}, ck)
-        ckpts.append(str(ck))
+    embs, ckpts, tok_flags = run_py_inputs(tmp_path)
     env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "tiny-newsrec_amd"))
     cmd = [sys.executable, "-u", os.path.join(ROOT, "tiny-newsrec_amd", "run.py"), "--mode", "train", "--enable_hvd", "False",
            "--train_data_dir", data, "--filename_pat", "behaviors_np4_*.tsv", "--batch_size", "4", "--epochs", "1",
            "--log_steps", "1", "--num_words_title", "30", "--news_dim", "256", "--num_student_layers", "2",
            "--bert_trainable_layer", "0", "1", "--num_teachers", "2", "--user_log_mask", "False", "--coef", "0.2",
-           "--model", "NAML", "--model_type", "tnlrv3", "--model_dir", str(tmp_path / "out"), "--tokenizer_name",
-           str(tmp_path / "vocab.txt"), "--config_name", str(tmp_path / "config.json"), "--model_name", str(tmp_path / "none.bin"), "--allow_random_init", "True",
+           "--model", "NAML", "--model_type", "tnlrv3", "--model_dir", str(tmp_path / "out")] + tok_flags + [
            "--teacher_emb_paths"] + embs + ["--teacher_ckpts"] + ckpts
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=os.path.join(ROOT, "tiny-newsrec_amd"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

@@ -118,7 +118,7 @@ def test_decode_process_yields_the_same_batches_as_the_producer_thread():
     import dataloader
 
     def collect(use_process):
-        dl, _ = _loader(batch_size=5)                 # no shuffle buffer: its generator is seeded from the OS, as tf.data's is
+        dl, _ = _loader(batch_size=5)                 # no shuffle buffer (with one: tests/test_filefed_data_cpu.py)
         dl.resident, dl.enable_gpu, dl.dedup, dl.decode_process = True, True, True, use_process
         dl._to_device = lambda h, m, c, y, plan: (np.asarray(h).copy(), np.asarray(m).copy(), np.asarray(c).copy(), np.asarray(y).copy(),
                                                   None if plan is None else (plan.uniq.copy(), plan.inv.copy(), plan.order.copy(),

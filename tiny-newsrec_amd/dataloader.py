@@ -28,7 +28,8 @@ class IndexBatch(tuple):
 
 
 class RowBatch(tuple):
-    """The reference's 6-tuple (dataloader.py:172) whose tensors came over in one staged copy (ready = its event)."""
+    """The reference's 6-tuple (dataloader.py:172); from the producer thread its tensors came over in one staged copy (ready =
+    its event).  plan: the batch's de-duplication plan (dedup.py) under --dedup_news, else None."""
 
 
 class DataLoaderTrain:
@@ -95,19 +96,30 @@ class DataLoaderTrain:
         out = [t(self.news_combined[h].astype(np.int64)), t(m), t(self.news_combined[c].astype(np.int64)), t(y),
                [t(np.asarray(te)[h].astype(np.float32)) for te in self.teacher_embs[:self.num_teachers]],
                [t(np.asarray(te)[c].astype(np.float32)) for te in self.teacher_embs[:self.num_teachers]]]
+        # --dedup_news in this mode too: the plan of the resident feed (the same h, c give the same plan), riding on the batch as
+        # `.plan` - the 6-tuple stays the reference's; the engine picks each distinct news' token row out of the rows it is given
+        plan = None
+        if self.dedup:
+            from dedup import build_plan
+            plan = build_plan(h, c)
         if self.enable_gpu and self.enable_prefetch and threading.current_thread() is self._thread:
-            return self._rows_to_device(out)                    # producer thread: one staged copy on its own stream
+            return self._rows_to_device(out, plan)              # producer thread: one staged copy on its own stream
         if self.enable_gpu:
             out = [x.cuda() if isinstance(x, torch.Tensor) else [v.cuda() for v in x] for x in out]
-        return tuple(out)
+            plan = plan.to("cuda") if plan is not None else None
+        res = RowBatch(out)
+        res.plan = plan
+        return res
 
-    def _rows_to_device(self, out):
+    def _rows_to_device(self, out, plan=None):
         """Reference mode from the producer thread: the reference's 4 + 2 T `.cuda()` calls (dataloader.py:160-170) are pageable copies
         on the default stream - 8.1 MB per step that queue between the training thread's kernels (+0.8 ms on a 7.6 ms step).  Here the
         same tensors leave as ONE pinned staging buffer and ONE asynchronous copy on the producer's own stream; the consumer's stream
         waits for its event (__next__).  Same 6-tuple, same values."""
         dev = torch.device("cuda", self.cuda_device_idx)
         flat = [out[0], out[1], out[2], out[3]] + list(out[4]) + list(out[5])
+        if plan is not None:                                    # the de-duplication plan's four index arrays ride in the same copy
+            flat += [torch.from_numpy(getattr(plan, k)) for k in ("uniq", "inv", "order", "seg")]
         words = [x.numpy().reshape(-1).view(np.int32) for x in flat]       # int64 parts as pairs of words
         off, offs = 0, []
         for a in words:
@@ -127,8 +139,15 @@ class DataLoaderTrain:
         slot[1] = ev
         dv = [d[o:o + n].view(x.dtype).view(x.shape) for x, (o, n) in zip(flat, offs)]
         T_ = len(out[4])
-        res = RowBatch((dv[0], dv[1], dv[2], dv[3], dv[4:4 + T_], dv[4 + T_:]))
+        res = RowBatch((dv[0], dv[1], dv[2], dv[3], dv[4:4 + T_], dv[4 + T_:4 + 2 * T_]))
         res.ready, res.buf = ev, d
+        res.plan = None
+        if plan is not None:
+            from dedup import DedupPlan
+            res.plan = DedupPlan()
+            for k, v in zip(("uniq", "inv", "order", "seg"), dv[4 + 2 * T_:]):
+                setattr(res.plan, k, v)
+            res.plan.n_enc, res.plan.n_unique, res.plan.n_slots = plan.n_enc, plan.n_unique, plan.n_slots
         return res
 
     def _to_device(self, h, m, c, y, plan):

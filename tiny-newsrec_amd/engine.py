@@ -1155,11 +1155,22 @@ class Engine:
                 T.call("tnr_gather_rows", self.Sv, plan.n_enc, plan.inv, N, D, 1, self.S, self.S.shape[0], 0)
         else:
             assert history.shape[1:] == (U, 2 * L) and candidate.shape[1:] == (C, 2 * L)
-            self.plan = None
+            self.plan = plan
             tok = self.tok[:N]
             tok[:B * U].copy_(history.reshape(B * U, 2 * L))
             tok[B * U:].copy_(candidate.reshape(B * C, 2 * L))
-            self.encode(tok, N, extra=extra)
+            if plan is None:
+                self.encode(tok, N, extra=extra)
+            else:
+                # the token rows fed by the host, de-duplicated as the resident feed is (dedup.py): the row of each distinct news
+                # is that of its first slot; the plan's padding entries (no slot, never gathered, zero gradient) are the all-zero
+                # pad news, as news_combined[0] is - the encoder then sees what it sees in the resident feed, row for row
+                assert plan.n_slots == N and plan.n_enc <= self.N_alloc
+                first = plan.order[plan.seg[:plan.n_unique].long()].long()
+                self.tok_u = torch.zeros((plan.n_enc, 2 * L), device=self.dev, dtype=tok.dtype)
+                self.tok_u[:plan.n_unique] = tok[first]
+                self.encode(self.tok_u, plan.n_enc, out=self.Sv, extra=extra)
+                T.call("tnr_gather_rows", self.Sv, plan.n_enc, plan.inv, N, D, 1, self.S, self.S.shape[0], 0)
         S = self.S[:Rt]
         g = self.p
         Qu = cfg.Qu

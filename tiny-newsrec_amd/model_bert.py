@@ -268,12 +268,13 @@ class Model(_Shell):
         optstate.check_header(osd, self.engine.dtype)
         self.engine.load_optimizer_state_dict(optstate.rekey(osd, self._engine_key))
 
-    def forward(self, history, history_mask, candidate, label, teacher_history_embs, teacher_candidate_embs):
+    def forward(self, history, history_mask, candidate, label, teacher_history_embs, teacher_candidate_embs, plan=None):
+        """plan: the loader's de-duplication plan of the batch (dedup.py, RowBatch.plan) or None; the reference has no such argument."""
         eng = self.engine
         if isinstance(history, tuple) and len(history) == 4:      # resident-mode IndexBatch
             raise TypeError("use forward_indexed for resident-mode batches")
         losses, score = eng.forward(history, history_mask, candidate, label, list(teacher_history_embs),
-                                    list(teacher_candidate_embs))
+                                    list(teacher_candidate_embs), plan=plan)
         return self._pack(losses, score)
 
     def forward_indexed(self, news_combined, hist_idx, history_mask, cand_idx, label, teacher_tables, plan=None):
@@ -346,8 +347,8 @@ class ModelBert(Model):
                          list(rep[0])[:8], len(rep[1]), list(rep[1])[:8])
         return rep
 
-    def forward(self, history, history_mask, candidate, label):
-        losses, score = self.engine.forward(history, history_mask, candidate, label)
+    def forward(self, history, history_mask, candidate, label, plan=None):
+        losses, score = self.engine.forward(history, history_mask, candidate, label, plan=plan)
         total = _Backward.apply(self._anchor, self, self.engine.total_loss())
         return total, score
 

@@ -163,7 +163,10 @@ def train(args):
                                  worker_rank=rank, cuda_device_idx=local, enable_prefetch=True, enable_shuffle=True,
                                  enable_gpu=True, resident=args.resident_tables)
         dev_news, dev_tab = getattr(loader, "dev_news", None), loader.dev_tables
-        batches = lambda: iter(loader)
+        # the loader itself, not iter(loader): the epoch loop's enumerate() calls __iter__, and every call of it starts an epoch
+        # (a producer, a re-sharding, the counter + 1) - two calls per epoch made the counter run two ahead of the seed epoch_cap()
+        # asks about, so the cap belonged to another file set than the one the epoch read
+        batches = lambda: loader
         if args.resume:
             loader.epoch = first_epoch - 1       # shard assignment and shuffle seeds go on as in the uninterrupted run
 
@@ -201,10 +204,10 @@ def train(args):
                     total, distill, emb, target, y_student = model.forward_indexed(dev_news, h, m, c, y, dev_tab, plan)
             elif plmnr:
                 h, m, c, y = batch[:4]
-                total, y_student = model(h, m, c, y)
+                total, y_student = model(h, m, c, y, plan=getattr(batch, "plan", None))
             else:
                 h, m, c, y, th, tc = batch
-                total, distill, emb, target, y_student = model(h, m, c, y, th, tc)
+                total, distill, emb, target, y_student = model(h, m, c, y, th, tc, plan=getattr(batch, "plan", None))
             loss_sum += total.detach()
             acc_sum += utils.acc(y, y_student)
             optimizer.zero_grad()

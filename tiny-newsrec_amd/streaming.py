@@ -126,7 +126,11 @@ class StreamSampler:
     def __init__(self, data_dir, filename_pat, batch_size, worker_rank, world_size, enable_shuffle=False,
                  shuffle_buffer_size=1000, shuffle_seed=0):
         paths = get_worker_files(data_dir, worker_rank, world_size, filename_pat, shuffle=enable_shuffle, seed=shuffle_seed)
-        self.stream_reader = StreamReader(paths, batch_size, enable_shuffle, shuffle_buffer_size)
+        # the reference leaves tf.data's shuffle buffer unseeded (streaming.py:72-74): any line order is a valid run of it.  Here
+        # the order follows the epoch number and the rank alone (a generator of the reader's own, a str seed is hashed the same
+        # way in every process), so that a run can be repeated and a --resume run reads the lines the uninterrupted run reads
+        self.stream_reader = StreamReader(paths, batch_size, enable_shuffle, shuffle_buffer_size,
+                                          seed="lines:%d:%d" % (shuffle_seed, worker_rank))
 
     def __iter__(self):
         self.stream_reader.reset()
