@@ -12,6 +12,11 @@ The plan is built by the loader's producer thread next to the sample decode (num
                             token count stays a multiple of 64 and only a few distinct workspace shapes occur
     inv   (N,)       int32  slot -> row of uniq
     order (N,)       int32  slots grouped by row of uniq (stable), seg (n_enc+1,) int32 the group offsets
+
+The 64-row rule.  The engine's weight-gradient kernels read their operands up to the next multiple of 64 token rows and need
+zeros behind the pass's own rows.  A plan's n_enc * L rows lie inside a workspace laid out for the whole batch, directly in front
+of rows that an earlier, larger pass has written, so n_enc * L must itself be a multiple of 64.  quantum = 64 gives that for every
+title length L; Engine.forward refuses (ValueError) a plan that breaks the rule, whatever quantum built it.
 """
 import numpy as np
 
@@ -31,7 +36,10 @@ class DedupPlan:
 
 def build_plan(hist_idx, cand_idx, quantum=64):
     """hist_idx (B,U), cand_idx (B,C) integer arrays -> DedupPlan (numpy members), or None when nothing would be
-    saved (padded distinct count >= slot count)."""
+    saved (padded distinct count >= slot count).
+    quantum: the distinct count is padded to a multiple of it.  Keep the default for a plan that Engine.forward is to run: the
+    engine takes a plan only if n_enc * L is a multiple of 64 (the 64-row rule above), which 64 guarantees for every L and a
+    smaller quantum only where quantum * L happens to be one."""
     slots = np.concatenate([np.asarray(hist_idx).reshape(-1), np.asarray(cand_idx).reshape(-1)]).astype(np.int64)
     n = slots.size
     uniq, inv = np.unique(slots, return_inverse=True)

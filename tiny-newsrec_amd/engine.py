@@ -1088,6 +1088,20 @@ class Engine:
         if B != self.B_alloc:
             self._alloc_workspace(B)
 
+    def _check_plan(self, plan, N):
+        """A de-duplication plan (dedup.py) this step can run, for both feeds.  The 64-row rule: the weight-gradient kernels
+        (tnr_gemm_tn_wgrad*) read dY and X up to roundup(M, 64) rows and need zeros behind row M.  An un-deduplicated pass has them:
+        the workspace is laid out for its batch and nothing writes behind its rows.  A plan's M = n_enc * L rows lie INSIDE that
+        workspace, with whatever an earlier, larger pass left directly behind them, so M itself has to be a multiple of 64 - which
+        build_plan's default quantum of 64 sequences gives for every L, and another quantum in general does not."""
+        L = self.cfg.L
+        if plan.n_slots != N or not 0 < plan.n_enc <= N:
+            raise ValueError("dedup plan for %d slots encoding %d sequences, but the batch has %d slots" % (plan.n_slots, plan.n_enc, N))
+        if (plan.n_enc * L) % 64:
+            raise ValueError("dedup plan encodes %d sequences x %d tokens = %d token rows, not a multiple of 64: the weight-gradient "
+                             "kernels read up to the next multiple of 64 rows and would sum an earlier pass's rows into this step's "
+                             "gradients; build the plan with quantum=64 (dedup.build_plan's default)" % (plan.n_enc, L, plan.n_enc * L))
+
     def forward_indexed(self, news_combined, hist_idx, history_mask, cand_idx, label, teacher_tables, plan=None):
         """The same step fed the way the resident-table loader feeds it: news_combined (n+1, 2L) int32 and
         teacher_tables (T, n+1, D) fp32 stay in HBM; per step only hist_idx (B,U), cand_idx (B,C) int32 news
@@ -1103,6 +1117,8 @@ class Engine:
         cfg = self.cfg
         B = history_mask.shape[0]
         U, C, L, D, T_ = cfg.U, cfg.C, cfg.L, cfg.D, cfg.T
+        if plan is not None:
+            self._check_plan(plan, B * (U + C))      # before anything is launched or re-laid
         self._prepare(B)
         N = B * (U + C)
         Rt = N + B
