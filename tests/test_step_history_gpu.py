@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 
 import engine as E                                               # noqa: E402
 import history_ref as HR                                         # noqa: E402
+import variants_ref as V                                         # noqa: E402
 import widths_ref as W                                           # noqa: E402
 
 DEV = "cuda:0"
@@ -33,10 +34,13 @@ def _t(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
 
-def _shared():
+def _shared(model=None):
+    """model: None = history_ref's model and weights, else a variant of tests/variants_ref.py (the feeds and tables are the same)."""
     if "comb" not in _DEV:
-        _DEV.update(comb=_t(HR.news()), tables=_t(HR.teachers()), P={k: _t(v) for k, v in HR.weights().items()})
-    return _DEV
+        _DEV.update(comb=_t(HR.news()), tables=_t(HR.teachers()))
+    if ("P", model) not in _DEV:
+        _DEV["P", model] = {k: _t(v) for k, v in (HR.weights() if model is None else V.weights(model)).items()}
+    return dict(comb=_DEV["comb"], tables=_DEV["tables"], P=_DEV["P", model])
 
 
 def _feed(fid, form):
@@ -49,8 +53,9 @@ def _feed(fid, form):
     return _DEV[fid, form]
 
 
-def _engine(dtype, B, **more):
-    return E.Engine(E.EngineConfig(**HR.engine_kwargs(), **more), DEV, max_batch=B, dtype=dtype)
+def _engine(dtype, B, model=None, **more):
+    kw = HR.engine_kwargs() if model is None else V.engine_kwargs(model)
+    return E.Engine(E.EngineConfig(**kw, **more), DEV, max_batch=B, dtype=dtype)
 
 
 def _set(eng, rec):
@@ -59,8 +64,9 @@ def _set(eng, rec):
         eng.scaler.mult = rec["mult"]
 
 
-def _run(eng, rec, plan=None):
-    """forward + backward of one record -> clones of what the rule compares."""
+def _run(eng, rec, plan=None, snap=False):
+    """forward + backward of one record -> clones of what the rule compares.  snap: under a bucket hook, each bucket's slice of
+    flat_g is cloned when its hook fires and must equal what the slice holds after backward (the bucket was complete)."""
     s = _shared()
     if plan is None and rec["plan"]:
         plan = HR.plan(rec["feed"]).to(DEV)
@@ -70,10 +76,17 @@ def _run(eng, rec, plan=None):
     else:
         hist, m, cand, y, th, tc = _feed(rec["feed"], "tok")
         losses, score = eng.forward(hist, m, cand, y, th, tc, plan=plan)
-    fired = []
-    eng.backward(after_bucket=fired.append if rec["hook"] else None, micro=rec["micro"])
+    fired, snaps, ranges = [], [], eng.bucket_ranges()
+
+    def hook(b):
+        fired.append(b)
+        if snap:
+            snaps.append(eng.flat_g[ranges[b][0]:ranges[b][1]].clone())
+    eng.backward(after_bucket=hook if rec["hook"] else None, micro=rec["micro"])
     if rec["hook"]:
         assert fired == list(range(len(eng.bucket_ranges()))) and len(fired) >= 3, fired     # every bucket, in completion order
+        for b, g in enumerate(snaps):
+            assert torch.equal(g, eng.flat_g[ranges[b][0]:ranges[b][1]]), "bucket %d changed after its hook fired" % b
     Rt = rec["B"] * (HR.U + HR.C + 1)
     assert eng.cur == (rec["B"], Rt - rec["B"], Rt)
     return dict(losses=losses.clone(), score=score.clone(), S=eng.S[:Rt].clone(), flat_g=eng.flat_g.clone())
@@ -88,7 +101,8 @@ def _act(eng, act, ctx):
     elif act[0] == "user_vectors":
         h, m, _, _ = _feed(act[1], "idx")
         uv = eng.user_vectors(ctx["ns"], h, m)
-        assert bool(torch.isfinite(uv).all()) and float(uv[1].abs().max()) > 0.0          # pad_doc stands in for a masked history
+        # pad_doc stands in for a masked history ; under user_log_mask nothing does: the pooling's weights are all masked
+        assert bool(torch.isfinite(uv).all()) and (float(uv[1].abs().max()) > 0.0) != bool(eng.cfg.user_log_mask)
     elif act[0] == "encode_news_eval":
         calls = eng.drop_calls
         ns = eng.encode_news(s["comb"])
@@ -115,10 +129,11 @@ def _act(eng, act, ctx):
         raise ValueError(act)
 
 
-def _play(dtype, schedule, eng, moving=False, after=None, ctx=None, **more):
+def _play(dtype, schedule, eng, moving=False, after=None, ctx=None, model=None, snap=False, **more):
     """Drive `eng` through the schedule; every step (accumulation window) against a fresh engine.  moving: the fresh engine takes
-    the long-lived engine's weights as they are in front of the step (else the shared initial ones).  after(n, window, results)."""
-    s, ctx, n = _shared(), ctx if ctx is not None else {}, 0
+    the long-lived engine's weights as they are in front of the step (else the shared initial ones).  after(n, window, results).
+    model, snap: as in _shared and _run."""
+    s, ctx, n = _shared(model), ctx if ctx is not None else {}, 0
     for win in HR.windows(schedule, dtype):
         for act in win[0]["pre"]:
             _act(eng, act, ctx)
@@ -127,13 +142,13 @@ def _play(dtype, schedule, eng, moving=False, after=None, ctx=None, **more):
         if moving and eng.f16:
             eng.scaler.drain(eng)
         sd = eng.state_dict() if moving else s["P"]
-        got = [_run(eng, r) for r in win]
+        got = [_run(eng, r, snap=snap) for r in win]
         assert eng.drop_calls == calls + (len(win) if win[0]["drop"] else 0)
-        fresh = _engine(dtype, win[0]["B"], **more)
+        fresh = _engine(dtype, win[0]["B"], model, **more)
         fresh.load_state_dict(sd)
         _set(fresh, win[0])
         fresh.drop_calls, fresh.scaler.mult = calls, mult
-        want = [_run(fresh, r) for r in win]
+        want = [_run(fresh, r, snap=snap) for r in win]
         torch.cuda.synchronize()
         for r, g, w in zip(win, got, want):
             n += 1
