@@ -574,6 +574,53 @@ int tnr_adamw_step_ema(float* p, const float* g, float* m, float* v, float* vmax
                        const unsigned* decay_bits, int64_t first, const unsigned* guard, unsigned stamp, unsigned known_skips,
                        const float* clip, float* ema, float w0, float w1, float w2, void* stream);
 
+/* LAMB (You et al., "Large Batch Optimization for Deep Learning", Algorithm 2): per-tensor trust ratios on the Adam / AMSGrad
+ * moments (the reference has none; an extension, engine.py: Engine.step(lamb=True)).  Per trainable tensor w, with g = grad_scale
+ * (x clip[0] when clip is given) x the flat gradient, exactly what tnr_adamw_step consumes:
+ *   1. m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2; vmax != NULL (AMSGrad): vhat = max(vmax, v), stored; else vhat = v.
+ *   2. r = (m / c1) / (sqrt(vhat) / sqrt(c2) + eps), c1 = 1 - b1^t, c2 = 1 - b2^t: the bias corrections of tnr_amsgrad_step.
+ *   3. u = r + weight_decay * w on the elements of a tensor of the decay set, u = r elsewhere.  The decay is COUPLED (it is part
+ *      of the update the trust ratio scales), not AdamW's p *= 1 - lr wd.
+ *   4. A tensor of the decay set is ADAPTED, whatever weight_decay is: trust = ||w||_2 / ||u||_2, or 1 if either norm is 0 (a
+ *      zero tensor can leave zero, a zero update divides nothing).  Every other tensor: trust = 1, the plain Adam update.  No
+ *      clamp, no phi; a NaN or infinite norm propagates into trust.
+ *   5. w <- w - lr_k * trust * u, then (ema != NULL) ema <- ema + w_k (w_new - ema) as tnr_adamw_step_ema does.
+ * The element-to-tensor map is a CHUNK TABLE made by the caller (engine.py: lamb_chunks): n_chunks entries of four int32 {first
+ * element, count in 1 .. 4096, tensor id, flags (bit 0: the tensor is in the decay set)}; a chunk never crosses its tensor's end,
+ * the chunks of a tensor are consecutive in the table, and what no chunk covers (alignment gaps, reserved rows) is neither read
+ * nor written.  `first` is an offset into p / g / m / v / vmax / ema, which are the WHOLE flat buffers (16-byte aligned, n
+ * elements, n < 2^31); a chunk may start at any element: 16-byte accesses where the absolute address allows, scalars at the
+ * unaligned head and tail.  The table is passed twice, on the device (16-byte aligned) and as the host's copy of the same entries,
+ * which is what the entry point checks before it launches.  The tensor table (tnr_lamb_commit) has n_tensors entries of four
+ * int32 {first chunk, number of chunks, adapted (0 / 1), 0}, on the device and on the host likewise.
+ *   tnr_lamb_norms: one workgroup per chunk forms m, v, vhat and u in registers, STORES NONE OF THEM, and writes part[2 j] = the
+ *     sum of w^2 and part[2 j + 1] = the sum of u^2 of the launch's j-th chunk if its flag is set (the partials of other chunks
+ *     are not written).  Fixed order: per lane four running sums (one per component of its 16-byte reads, scalars into the
+ *     first), their pairwise sum, the 64 lanes by butterfly, the four waves in wave order, one plain store.
+ *   tnr_lamb_commit: per tensor, the partials of its chunks summed in double in a fixed order -> trust[t], and for diagnostics
+ *     trust[n_tensors + t] = ||w||, trust[2 n_tensors + t] = ||u|| (3 n_tensors floats; not adapted: 1, 0, 0).
+ *   tnr_lamb_step: the same chunks (any consecutive part of the table, so that ranges with different rates get a launch each):
+ *     recomputes m, v, vhat, u by the same expressions - the same bits as in the norm pass -, stores the moments, updates w with
+ *     trust[tensor], then the average.  lr_k, w_k: the three candidates of tnr_adamw_step_ema.
+ * Guard (nullable) and candidates as in tnr_amsgrad_step_guarded: each of the three launches, stamped guard[0], returns before
+ * touching p, m, v, vmax, ema, part and trust; otherwise the bias corrections, the rate and the average's weight are those of
+ * candidate min(guard[1] - known_skips, 2), the SAME one in the norm pass and the apply pass (u depends on c1 and c2).  No float
+ * atomics and no arrival counters: the bits of trust and of every buffer are a function of the inputs alone.
+ * Errors (no launch): a NULL or misaligned buffer or table, n_chunks < 1, n_tensors < 1, a chunk outside [0, n) or with a count
+ * outside 1 .. 4096 or a tensor id >= n_tensors, a tensor whose chunks lie outside [0, n_chunks), step < 1, weight_decay < 0, a
+ * guard with stamp 0, and for tnr_lamb_step with an average a weight outside [0, 1].  Stream-ordered, no host synchronisation. */
+int tnr_lamb_norms(const float* p, const float* g, const float* m, const float* v, const float* vmax, int64_t n,
+                   const int32_t* chunks, const int32_t* chunks_host, int64_t n_chunks, int n_tensors, int step, float beta1,
+                   float beta2, float eps, float grad_scale, float weight_decay, const unsigned* guard, unsigned stamp,
+                   unsigned known_skips, const float* clip, float* part, void* stream);
+int tnr_lamb_commit(const float* part, int64_t n_chunks, const int32_t* tensors, const int32_t* tensors_host, int n_tensors,
+                    float* trust, const unsigned* guard, unsigned stamp, void* stream);
+int tnr_lamb_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const int32_t* chunks,
+                  const int32_t* chunks_host, int64_t n_chunks, int n_tensors, int step, float lr0, float lr1, float lr2,
+                  float beta1, float beta2, float eps, float grad_scale, float weight_decay, const unsigned* guard, unsigned stamp,
+                  unsigned known_skips, const float* clip, const float* trust, float* ema, float w0, float w1, float w2,
+                  void* stream);
+
 /* refresh bf16 weight copies after an update: desc = n_desc * 8 int64 on DEVICE:
  * {src fp32 ptr, rows, cols, dst ptr (or 0), dst ld, dstT ptr (or 0), dstT ld, unused}
  * dst[r*ld + c] = bf16(src[r,c]) ; dstT[c*ldT + r] = bf16(src[r,c]), round to nearest even.  Only [0, rows) x [0, cols) of

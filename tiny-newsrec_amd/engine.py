@@ -264,6 +264,32 @@ def decay_words(slot, n_train):
     return np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).copy()
 
 
+LAMB_CHUNK = 4096       # elements per chunk at most (csrc/lamb.hip: one workgroup of 256 lanes x 4 x 16 bytes)
+
+
+def lamb_chunks(slot, n_train):
+    """The element-to-tensor map of step(lamb=True), a pure host function of the slot table like decay_words:
+    (names, chunks, tensors).  names: the trainable tensors in the order of their offsets; the index is the tensor id.
+    chunks: int32 (n_chunks, 4) rows (first element, count, tensor id, flags), flags bit 0 = decays(name, shape) (the adapted
+    set).  A chunk never crosses its tensor's end and holds 1 .. LAMB_CHUNK elements; inside a tensor chunks end at absolute
+    multiples of LAMB_CHUNK, so that only a tensor's first chunk can start off a 16-byte boundary.  Together they cover every
+    element of every trainable tensor exactly once and nothing else: alignment gaps and reserved rows belong to no chunk.
+    tensors: int32 (n_tensors, 4) rows (first chunk, number of chunks, adapted, 0); a tensor's chunks are consecutive."""
+    names = sorted((k for k, s in slot.items() if s[0] and s[2] > 0), key=lambda k: slot[k][1])
+    chunks, tensors = [], []
+    for t, name in enumerate(names):
+        _, o, n, shp = slot[name]
+        assert 0 <= o and o + n <= n_train, name
+        flag = 1 if decays(name, shp) else 0
+        first_chunk, pos = len(chunks), o
+        while pos < o + n:
+            end = min(o + n, (pos // LAMB_CHUNK + 1) * LAMB_CHUNK)
+            chunks.append((pos, end - pos, t, flag))
+            pos = end
+        tensors.append((first_chunk, len(chunks) - first_chunk, flag, 0))
+    return (names, np.asarray(chunks, dtype=np.int32).reshape(-1, 4), np.asarray(tensors, dtype=np.int32).reshape(-1, 4))
+
+
 LOSS_SCALE = 1024.0     # static scale of the 16-bit backward in fp16 mode (gradients of ~1e-6 would underflow); it enters at
                         # the pooling backward and leaves in the kernels that write parameter gradients (weight-gradient slab
                         # reduce, bias / LayerNorm partial reductions), so flat_g always holds the true gradients
@@ -368,6 +394,7 @@ class Engine:
         self._decay_map = None       # step(weight_decay > 0): the owner's decay bits on the device, made on first use
         self.lr_scale = None         # the host's multiplier of the last step's learning rates while a schedule is on, else None
         self._ema = None             # step(ema_decay > 0): the owner's average of flat[True], made on first use
+        self._lamb_state = None      # step(lamb=True): the owner's chunk / tensor / trust tables and partial buffer, made on first use
         self._ema_updates = [0, 0]   # updates counted into it, and the scaler's skipped-step total that count already reflects
         self._acc = None             # backward(micro=(j, K > 1)): the owner's accumulator of flat_g over a window, made on first use
         self._acc_held = 0           # micro-gradients the owner's accumulator holds (0 outside an accumulation window)
@@ -1695,6 +1722,36 @@ class Engine:
             own._decay_map = torch.from_numpy(words.view(np.int32)).to(own.dev)
         return own._decay_map
 
+    def _lamb_buffers(self):
+        """State of step(lamb=True), made on first use by the engine that owns flat_g (engines built with share= use it, so a
+        shared slot table yields ONE chunk table): lamb_chunks of the slot table on the host and on the device, two fp32
+        partials per chunk, the trust table (trust, ||w||, ||u|| per tensor) and a pinned ring for its read-back."""
+        own = self._clip_owner
+        if own._lamb_state is None:
+            names, chunks, tensors = lamb_chunks(own.slot, own.n_train)
+            ch, tn = torch.from_numpy(chunks).contiguous(), torch.from_numpy(tensors).contiguous()
+            nt = len(names)
+            own._lamb_state = SimpleNamespace(
+                names=names, chunks_host=ch, tensors_host=tn, chunks=ch.to(own.dev), tensors=tn.to(own.dev), n_chunks=len(chunks),
+                n_tensors=nt, firsts=chunks[:, 0].astype(np.int64), adapted=[i for i in range(nt) if tensors[i, 2]],
+                part=torch.zeros(2 * len(chunks), dtype=torch.float32, device=own.dev),
+                trust=torch.zeros(3 * nt, dtype=torch.float32, device=own.dev),
+                ring=torch.zeros(8, 3 * nt, dtype=torch.float32).pin_memory(), count=0, last=None)
+        return own._lamb_state
+
+    def trust_ratios(self):
+        """{name: (trust, ||w||, ||u||)} of the adapted tensors (the decay set) at the last step(lamb=True): the ratio the update
+        of that tensor was multiplied by and the two norms it came from (w before the update).  Read back like grad_norm(): step()
+        queued a copy into pinned memory and an event behind its last launch, and this waits for that event only.  None before
+        the first such step.  fp16: a step the overflow guard skipped leaves the table of the step before it."""
+        ls = self._clip_owner._lamb_state
+        if ls is None or ls.last is None:
+            return None
+        host, ev = ls.last
+        ev.synchronize()
+        nt = ls.n_tensors
+        return {ls.names[i]: (float(host[i]), float(host[nt + i]), float(host[2 * nt + i])) for i in ls.adapted}
+
     def _ema_buffer(self):
         """The average of flat[True] (step(ema_decay > 0)): fp32, laid out like flat[True], made on first use by the engine that
         owns flat[True] as a copy of the parameters as they are now, on the current stream (the first step with the average on
@@ -1804,7 +1861,7 @@ class Engine:
         self.drop_calls = int(osd["dropout_calls"])
 
     def step(self, lr, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, lr_bert=None, amsgrad=True, lr_news_head=None, sync=None,
-             max_grad_norm=None, weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=None, ema_warmup=False):
+             max_grad_norm=None, weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=None, ema_warmup=False, lamb=False):
         """torch.optim.Adam(amsgrad=True).step() (run.py:134,195) + refresh of the 16-bit weight copies.
         lr_bert / lr_news_head: learning rates of the encoder layers / of the news encoder's pooling + dense when they
         differ (PLM-NR/run.py:104-106: {'params': pretrained, 'lr': pretrain_lr}, {'params': rest, 'lr': lr}; the notebooks
@@ -1842,8 +1899,20 @@ class Engine:
         calls, kernels, bits and buffers of a step without it.
         Gradient accumulation (backward(micro=(j, K))) adds nothing here but an assertion: the window's mean is grad_scale =
         1 / (world * K) on the summed flat_g, so the clip norm, the guard, the decay, the schedule and the average see what torch
-        shows them after K backwards of loss / K, with no extra pass."""
+        shows them after K backwards of loss / K, with no extra pass.
+        lamb=True: LAMB (You et al., Algorithm 2; the contract: include/tnr_hip.h).  The moments are Adam's /
+        AMSGrad's; per tensor of the slot table u = (m / c1) / (sqrt(vhat) / sqrt(c2) + eps) + weight_decay * w on the decay set
+        (u without the decay term elsewhere), and w <- w - lr_k * trust * u with trust = ||w|| / ||u|| for the tensors of the
+        decay set (whatever weight_decay is; 1 if either norm is 0) and 1 for every other tensor: biases, LayerNorm parameters
+        and pad_doc take the plain Adam update.  weight_decay is then this COUPLED decay, not AdamW's.  A tensor's norm needs its
+        whole gradient, so with a pending sync the step waits for every bucket first, in bucket_ranges() order, scanning each as
+        it lands when clip or the guard is on (the scans and commits are today's); then tnr_lamb_norms over the whole chunk table,
+        tnr_lamb_commit, tnr_lamb_step per rate range.  No tnr_amsgrad_step* / tnr_adamw_step* call is made, no new optimiser state
+        exists (optimizer_state_dict() is unchanged) and nothing is communicated: the trust ratios are a deterministic function of
+        buffers that are identical on every rank.  trust_ratios() reads the result back.  False / None: off - the calls, kernels,
+        bits and buffers of a step without it, nothing allocated."""
         assert self._clip_owner._acc_held == 0, "step() inside an accumulation window"
+        lamb_on = bool(lamb)
         clip_on = max_grad_norm is not None and max_grad_norm > 0
         ema_d = float(ema_decay or 0.0)
         ema_on = ema_d > 0.0
@@ -1864,8 +1933,8 @@ class Engine:
         if adamw_on:
             # candidates k = 0, 1, 2: t_k = max(step_count - k, 1) updates taken including this one (the launcher's t_k)
             mult = [lr_schedule(max(self.step_count - k, 1) - 1, W_, Td) for k in range(3)]
-            wbits = self._decay_bits() if wd > 0.0 else None
-        elif ema_on:
+            wbits = self._decay_bits() if wd > 0.0 and not lamb_on else None
+        elif ema_on or lamb_on:
             mult, wbits = (1.0, 1.0, 1.0), None
         self.lr_scale = mult[0] if sched_on else None
         if ema_on:
@@ -1902,7 +1971,63 @@ class Engine:
                 else:
                     T.call("tnr_amsgrad_step_guarded", *args, guard, stamp, sc.skipped)
 
-        if clip_on:
+        if lamb_on:
+            ls = self._lamb_buffers()
+            cs = self._clip_buffers() if clip_on else None
+            bucketed = sync is not None and sync.pending
+            slices = [(s_, e_) for s_, e_, _ in cs.slices] if clip_on else (list(sync.ranges) if bucketed else [])
+            if bucketed:
+                assert [tuple(r) for r in sync.ranges] == [tuple(r) for r in self.bucket_ranges()], "sync buckets are not bucket_ranges()"
+            elif sync is not None:
+                sync.wait()
+            # the whole (reduced) gradient first: every bucket in completion order, scanned as it lands when clip or the guard is on
+            if clip_on:
+                for b, (s_, e_, off) in enumerate(cs.slices):
+                    if bucketed:
+                        sync.wait_bucket(b)
+                    T.call("tnr_grad_sumsq_scan", self.flat_g[s_:e_], e_ - s_, cs.part[off:], guard, stamp)
+                if guard is not None:
+                    T.call("tnr_grad_nonfinite_commit", guard, stamp)
+                T.call("tnr_grad_clip_commit", cs.part, cs.n_part, float(max_grad_norm), grad_scale, cs.clip)
+            elif bucketed:
+                for b, (s_, e_) in enumerate(slices):
+                    sync.wait_bucket(b)
+                    if guard is not None:
+                        T.call("tnr_grad_nonfinite_scan", self.flat_g[s_:e_], e_ - s_, guard, stamp)
+                if guard is not None:
+                    T.call("tnr_grad_nonfinite_commit", guard, stamp)
+            elif guard is not None:
+                T.call("tnr_grad_nonfinite", self.flat_g, self.n_train, guard, stamp)
+            known = sc.skipped if guard is not None else 0
+            clip_ = cs.clip if clip_on else None
+            vmax_ = self.adam_vmax if amsgrad else None
+            T.call("tnr_lamb_norms", self.flat[True], self.flat_g, self.adam_m, self.adam_v, vmax_, self.n_train, ls.chunks,
+                   ls.chunks_host, ls.n_chunks, ls.n_tensors, self.step_count, beta1, beta2, eps, grad_scale, wd, guard, stamp,
+                   known, clip_, ls.part)
+            T.call("tnr_lamb_commit", ls.part, ls.n_chunks, ls.tensors, ls.tensors_host, ls.n_tensors, ls.trust, guard, stamp)
+            for lo_, hi_, rate in ranges:
+                c0, c1 = int(np.searchsorted(ls.firsts, lo_)), int(np.searchsorted(ls.firsts, hi_))
+                if c1 > c0:      # a rate range starts and ends where a storage group does, so no chunk straddles its bounds
+                    T.call("tnr_lamb_step", self.flat[True], self.flat_g, self.adam_m, self.adam_v, vmax_, self.n_train,
+                           ls.chunks[c0:c1], ls.chunks_host[c0:c1], c1 - c0, ls.n_tensors, self.step_count, rate * mult[0],
+                           rate * mult[1], rate * mult[2], beta1, beta2, eps, grad_scale, wd, guard, stamp, known, clip_, ls.trust,
+                           ema if ema_on else None, *(ema_w if ema_on else (0.0, 0.0, 0.0)))
+            if guard is not None:
+                sc.record(used)
+            if clip_on:
+                host = cs.ring[cs.count % 8]
+                cs.count += 1
+                host.copy_(cs.clip, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                cs.last = (host, ev)
+            host = ls.ring[ls.count % 8]
+            ls.count += 1
+            host.copy_(ls.trust, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            ls.last = (host, ev)
+        elif clip_on:
             cs = self._clip_buffers()
             bucketed = sync is not None and sync.pending
             if bucketed:

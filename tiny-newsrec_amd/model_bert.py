@@ -363,7 +363,7 @@ class TnrAdam:
     (one fused kernel + bf16-copy refresh); zero_grad / step keep the reference's call order (run.py:193-195)."""
 
     def __init__(self, model, lr, grad_sync=None, pretrain_lr=None, pretrained_heads=False, max_grad_norm=0.0,
-                 weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=0.0, ema_warmup=False, grad_accum_steps=1):
+                 weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=0.0, ema_warmup=False, grad_accum_steps=1, optimizer="adam"):
         """pretrain_lr: PLM-NR/run.py:104-106 - the "pretrained" parameters step with their own rate: the encoder layers,
         and (pretrained_heads) the news encoder's pooling + dense when they came from the first-stage checkpoint too.
         max_grad_norm > 0: clip_grad_norm_ inside the engine's step, behind the gradient all-reduce (a clip_grad_norm_ between
@@ -376,7 +376,12 @@ class TnrAdam:
         owns the position in the window and publishes (j, K) on the model, whose backward hands it to Engine.backward(micro=):
         the engine sums the K gradients (under data parallelism the all-reduces start in the K-th backward only and carry the
         sum).  step() number 1 .. K - 1 of a window only advances the position; the K-th is the engine's step with grad_scale =
-        1 / (world * K).  reset_window() drops a partial window.  Not with strict_grad_scale.  1 = off: today's calls."""
+        1 / (world * K).  reset_window() drops a partial window.  Not with strict_grad_scale.  1 = off: today's calls.
+        optimizer = "lamb": per-tensor trust ratios on the same moments (Engine.step(lamb=True)); weight_decay is then LAMB's coupled
+        decay.  "adam" = off: today's calls."""
+        if optimizer not in ("adam", "lamb"):
+            raise ValueError("optimizer must be 'adam' or 'lamb', got %r" % (optimizer,))
+        self.optimizer = optimizer
         self.model, self.lr, self.grad_sync, self.pretrain_lr = model, lr, grad_sync, pretrain_lr
         self.pretrained_heads = pretrained_heads
         self.max_grad_norm = float(max_grad_norm or 0.0)
@@ -434,4 +439,5 @@ class TnrAdam:
                                **({"weight_decay": self.weight_decay, "warmup_steps": self.warmup_steps,
                                    "lr_decay_steps": self.lr_decay_steps}
                                   if (self.weight_decay > 0 or self.warmup_steps > 0 or self.lr_decay_steps > 0) else {}),
-                               **({"ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup} if self.ema_decay > 0 else {}))
+                               **({"ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup} if self.ema_decay > 0 else {}),
+                               **({"lamb": True} if self.optimizer == "lamb" else {}))

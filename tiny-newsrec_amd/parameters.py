@@ -41,7 +41,8 @@ def _flag_table():
           # additions (defaults keep the reference behaviour)
           ("train_embeddings", _B, False, dict(help="also fine-tune bert.embeddings.* (word / position / token-type tables and the embedding LayerNorm) at the encoder's learning rate; the reference freezes them (run.py:101-112); needs --bert_trainable_layer")),
           ("max_grad_norm", float, 0.0, dict(help="clip the gradient by its global L2 norm, torch.nn.utils.clip_grad_norm_ semantics (one norm over everything trainable, coef = min(1, max_norm / (norm + 1e-6))), done on the device after the gradient all-reduce; 0 = off (the reference does not clip)")),
-          ("weight_decay", float, 0.0, dict(help="decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * weight_decay before the Adam / AMSGrad update) of the 2-D weights outside LayerNorm - biases, LayerNorm parameters and pad_doc are exempt; with --train_embeddings the embedding tables decay - inside the fused update; 0 = off (the reference uses Adam without decay)")),
+          ("weight_decay", float, 0.0, dict(help="decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * weight_decay before the Adam / AMSGrad update; with --optimizer lamb: LAMB's coupled decay instead, weight_decay * w added to the update that the trust ratio scales) of the 2-D weights outside LayerNorm - biases, LayerNorm parameters and pad_doc are exempt; with --train_embeddings the embedding tables decay - inside the fused update; 0 = off (the reference uses Adam without decay)")),
+          ("optimizer", str, "adam", dict(choices=["adam", "lamb"], help="lamb: LAMB (You et al., Large Batch Optimization for Deep Learning, Algorithm 2) on the same Adam / AMSGrad moments, inside the fused update: the step of every 2-D weight outside LayerNorm is rescaled by its trust ratio ||w|| / ||update|| (no clamp; biases, LayerNorm parameters and pad_doc take the plain Adam step), for batches in the thousands (--grad_accum_steps x --batch_size x workers). --weight_decay then means LAMB's COUPLED decay - weight_decay * w is added to the update before the trust ratio scales it - not AdamW's p *= 1 - lr * weight_decay. No new optimiser state: --save_optimizer / --resume work as with adam. The trust ratios (min / median / max) are logged every --log_steps; adam = off (the reference's optimiser)")),
           ("warmup_steps", int, 0, dict(help="multiply every learning rate by u / warmup_steps over the first warmup_steps updates (u = updates taken so far: the first update has rate 0; steps skipped for an fp16 overflow do not count); 0 = no warmup (the reference's rate is constant). The schedule's position is optimiser state: --save_optimizer True writes it into the epoch checkpoint with the Adam moments, and --resume True continues from it (without them a restarted run ramps again from rate 0)")),
           ("lr_decay_steps", int, 0, dict(help="after the warmup, decay every learning rate linearly to 0 at update lr_decay_steps (transformers' get_linear_schedule_with_warmup with num_training_steps = lr_decay_steps), 0 from there on; 0 = constant after the warmup (the reference's rate is constant). The position is saved by --save_optimizer True and restored by --resume True, like the Adam moments")),
           ("ema_decay", float, 0.0, dict(help="keep an exponential moving average of the trainable parameters, ema = ema_decay * ema + (1 - ema_decay) * p after every update (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn), inside the fused update; steps skipped for an fp16 overflow do not advance it. The epoch checkpoint then also holds ema_state_dict (same keys as model_state_dict) and ema (decay, warmup, updates), and --load_ckpt_name resumes the average from it; 0 = off (the reference keeps no average)")),

@@ -67,7 +67,12 @@ def parse_args(argv=None):
     p.add_argument("--weight_decay", type=float, default=0.0,
                    help="decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * weight_decay before the Adam update) of the 2-D weights "
                         "outside LayerNorm (biases and LayerNorm parameters are exempt), inside the fused update; 0 = off (the notebooks "
-                        "use Adam without decay)")
+                        "use Adam without decay). With --optimizer lamb: LAMB's coupled decay instead, weight_decay * w added to the "
+                        "update that the trust ratio scales")
+    p.add_argument("--optimizer", default="adam", choices=["adam", "lamb"],
+                   help="lamb: LAMB (You et al., Algorithm 2) on the same Adam moments inside the fused update - the step of every 2-D "
+                        "weight outside LayerNorm is rescaled by its trust ratio ||w|| / ||update|| (biases and LayerNorm parameters take "
+                        "the plain Adam step); --weight_decay then means LAMB's coupled decay; adam = off (the notebooks' optimiser)")
     p.add_argument("--warmup_steps", type=int, default=0,
                    help="multiply both learning rates by u / warmup_steps over the first warmup_steps updates (u = updates taken so far: the "
                         "first update has rate 0; steps skipped for an fp16 overflow do not count); 0 = no warmup (the notebooks' rates are "
@@ -266,6 +271,8 @@ def train(args):
                 clip_kw = dict(clip_kw, weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps)
             if args.ema_decay > 0:
                 clip_kw = dict(clip_kw, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+            if args.optimizer == "lamb":
+                clip_kw = dict(clip_kw, lamb=True)
             eng.step(args.lr, grad_scale=sync.scale if sync else 1.0, lr_bert=args.pretrain_lr, amsgrad=False, sync=sync, **clip_kw)
             if args.stage == 0 and rank == 0 and cnt % args.save_steps == 0:          # cell 16: DP_12_layer_{cnt}.pt
                 os.makedirs(args.save_dir, exist_ok=True)
@@ -275,6 +282,10 @@ def train(args):
                 s = (sums / cnt).tolist()
                 sc = eng.title.scaler
                 gn = eng.grad_norm() if args.max_grad_norm > 0 else None
+                tr = eng.trust_ratios() if args.optimizer == "lamb" else None
+                if tr:
+                    tv = sorted(t for t, _, _ in tr.values())
+                    logging.info("[%d] trust ratio min %g / median %g / max %g over %d tensors" % (rank, tv[0], tv[len(tv) // 2], tv[-1], len(tv)))
                 logging.info("[%d] ed: %d, loss: %.5f, t_loss: %.5f, d_loss: %.5f, e_loss: %.5f, acc: %.5f, %.1f pairs/s%s%s%s" % (
                     rank, cnt * B, s[0], s[1], s[2], s[3], s[4], size * cnt * B / max(time.time() - t0, 1e-9),
                     ", loss scale %g, %d steps skipped (fp16 overflow)" % (eng.title.gscale, sc.skipped) if sc.enabled and sc.skipped else "",

@@ -34,11 +34,15 @@ def _load_inputs(args):
 
 
 def _train_flags(args, world):
-    """The flags a --save_optimizer checkpoint records (train_state["flags"]): what a --resume run compares its own against."""
+    """The flags a --save_optimizer checkpoint records (train_state["flags"]): what a --resume run compares its own against.
+    `optimizer` is recorded when it is not the default: a checkpoint of an adam run holds the flags it always held, and a
+    checkpoint without the key was written by adam."""
     names = ("lr", "pretrain_lr", "weight_decay", "warmup_steps", "lr_decay_steps", "ema_decay", "ema_warmup", "grad_accum_steps",
              "max_grad_norm", "batch_size", "dtype")
     flags = {k: getattr(args, k) for k in names}
     flags["world"] = world
+    if getattr(args, "optimizer", "adam") != "adam":
+        flags["optimizer"] = args.optimizer
     return flags
 
 
@@ -111,7 +115,8 @@ def train(args):
                         pretrain_lr=args.pretrain_lr if (plmnr and pretrained) else None,      # PLM-NR/run.py:94-106
                         pretrained_heads=plmnr and pretrained, max_grad_norm=args.max_grad_norm,
                         weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps,
-                        ema_decay=args.ema_decay, ema_warmup=args.ema_warmup, grad_accum_steps=args.grad_accum_steps)
+                        ema_decay=args.ema_decay, ema_warmup=args.ema_warmup, grad_accum_steps=args.grad_accum_steps,
+                        optimizer=args.optimizer)
     accum_logged = False
     first_epoch = args.start_epoch
     if args.resume:
@@ -125,8 +130,8 @@ def train(args):
         first_epoch = int(ts["epoch"])
         if args.start_epoch not in (0, first_epoch):
             raise ValueError(f"--resume True: {ck} was written at the end of epoch {first_epoch}, --start_epoch says {args.start_epoch}")
-        mine = _train_flags(args, size)
-        for k, v in ts.get("flags", {}).items():
+        mine = dict(_train_flags(args, size), optimizer=args.optimizer)
+        for k, v in dict(ts.get("flags", {}), optimizer=ts.get("flags", {}).get("optimizer", "adam")).items():
             if k in mine and mine[k] != v:
                 logging.warning(f"--resume True: --{k} is {mine[k]}, the run that wrote {ck} had {v}" if k != "world" else
                                 f"--resume True: {size} worker(s), the run that wrote {ck} had {v}")
@@ -217,6 +222,11 @@ def train(args):
                 d = max(cnt, 1)
                 sc = eng.scaler          # fp16: steps whose 16-bit backward overflowed are skipped on the device (engine.LossScaler)
                 gn = eng.grad_norm() if args.max_grad_norm > 0 else None     # this step's norm after the all-reduce, and its clip
+                tr = eng.trust_ratios() if args.optimizer == "lamb" else None      # this step's LAMB ratios over the adapted tensors
+                if tr:
+                    tv = sorted(t for t, _, _ in tr.values())
+                    logging.info("[{}] trust ratio min {:g} / median {:g} / max {:g} over {} tensors".format(
+                        rank, tv[0], tv[len(tv) // 2], tv[-1], len(tv)))
                 logging.info("[{}] Ed: {}, train_loss: {:.5f}, acc: {:.5f}, {:.1f} impressions/s{}{}{}".format(
                     rank, cnt * args.batch_size, loss_sum.item() / d, acc_sum.item() / d,
                     size * cnt * args.batch_size / max(time.time() - t0, 1e-9),

@@ -364,8 +364,8 @@ class Stage1Engine:
 
     def step(self, lr, grad_scale=1.0, lr_bert=None, amsgrad=False, **kw):
         """Post-train_KD.ipynb cell 18: optim.Adam([{bert_model, 1e-6}, {rest, 1e-5}]) (plain Adam by default here).
-        kw: Engine.step's sync, max_grad_norm, weight_decay, warmup_steps, lr_decay_steps, ema_decay, ema_warmup (one decay map,
-        one schedule position, one average: the title engine owns the shared buffers)."""
+        kw: Engine.step's sync, max_grad_norm, weight_decay, warmup_steps, lr_decay_steps, ema_decay, ema_warmup, lamb (one decay map,
+        one schedule position, one average, one chunk table: the title engine owns the shared buffers)."""
         self.title.step(lr, grad_scale, lr_bert=lr_bert, amsgrad=amsgrad, **kw)
 
     @property
@@ -376,3 +376,7 @@ class Stage1Engine:
     def grad_norm(self):
         """Engine.grad_norm of the last step(max_grad_norm=...): one norm over the title + body gradient (one flat buffer)."""
         return self.title.grad_norm()
+
+    def trust_ratios(self):
+        """Engine.trust_ratios of the last step(lamb=True): one chunk table over the shared flat buffer."""
+        return self.title.trust_ratios()

@@ -172,6 +172,10 @@ _SIG = {
     "tnr_adamw_step": [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _L, _P, _c.c_uint, _c.c_uint, _P, _P],
     "tnr_adamw_step_ema": [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _L, _P, _c.c_uint, _c.c_uint, _P,
                            _P, _F, _F, _F, _P],
+    "tnr_lamb_norms": [_P, _P, _P, _P, _P, _L, _P, _P, _L, _I, _I, _F, _F, _F, _F, _F, _P, _c.c_uint, _c.c_uint, _P, _P, _P],
+    "tnr_lamb_commit": [_P, _L, _P, _P, _I, _P, _P, _c.c_uint, _P],
+    "tnr_lamb_step": [_P, _P, _P, _P, _P, _L, _P, _P, _L, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _c.c_uint, _c.c_uint, _P,
+                      _P, _P, _F, _F, _F, _P],
     "tnr_refresh_shadows": [_P, _I, _L, _P, _P],
     "tnr_cast_f32_to_bf16": [_P, _P, _L, _P],
     "tnr_cast_bf16_to_f32": [_P, _P, _L, _P],
