@@ -1395,13 +1395,20 @@ class Engine:
             self.backward(after_bucket=fold_then)
         own._acc_held = 0
 
+    def _owned(self, attr, make):
+        """State that a mode of the step needs and that no other mode pays for: attribute `attr` of the engine that owns flat_g
+        (engines built with share= use the owner's), made by make(owner) on first use.  Never requested, nothing is allocated."""
+        own = self._clip_owner
+        state = getattr(own, attr)
+        if state is None:
+            state = make(own)
+            setattr(own, attr, state)
+        return state
+
     def _acc_buffer(self):
         """The accumulator of a gradient-accumulation window (backward(micro=...)): fp32, laid out like flat_g, made on first use
         by the engine that owns flat_g; engines built with share= use the owner's.  Never requested, nothing is allocated."""
-        own = self._clip_owner
-        if own._acc is None:
-            own._acc = torch.zeros_like(own.flat_g)
-        return own._acc
+        return self._owned("_acc", lambda own: torch.zeros_like(own.flat_g))
 
     def accum_reset(self):
         """Drop a partial accumulation window (an epoch that ends inside one): the next backward(micro=(0, K)) overwrites
@@ -1690,54 +1697,64 @@ class Engine:
         """State of global-norm clipping, made on first use by the engine that owns flat_g (engines built with share= use it):
         the scanned slices (bucket_ranges()) with the offset of each one's partial sums, the partial buffer sized through
         tnr_grad_sumsq_parts, the two floats (coefficient, norm) on the device and a pinned ring for their read-back."""
-        own = self._clip_owner
-        if own._clip_state is None:
+        def make(own):
             slices, off = [], 0
             for s_, e_ in own.bucket_ranges():
                 slices.append((s_, e_, off))
                 off += T.query("tnr_grad_sumsq_parts", e_ - s_)
-            own._clip_state = SimpleNamespace(slices=slices, n_part=off, part=torch.zeros(off, dtype=torch.float32, device=own.dev),
-                                              clip=torch.zeros(2, dtype=torch.float32, device=own.dev),
-                                              ring=torch.zeros(8, 2, dtype=torch.float32).pin_memory(), count=0, last=None)
-        return own._clip_state
+            return SimpleNamespace(slices=slices, n_part=off, part=torch.zeros(off, dtype=torch.float32, device=own.dev),
+                                   clip=torch.zeros(2, dtype=torch.float32, device=own.dev),
+                                   ring=torch.zeros(8, 2, dtype=torch.float32).pin_memory(), count=0, last=None)
+        return self._owned("_clip_state", make)
+
+    @staticmethod
+    def _read_back(st, src):
+        """Queue a copy of `src` into the next slot of st.ring (pinned, 8 slots) and an event behind it, and keep (host, event)
+        in st.last: the step never waits for a figure it only reports."""
+        host = st.ring[st.count % 8]
+        st.count += 1
+        host.copy_(src, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        st.last = (host, ev)
+
+    @staticmethod
+    def _last_read_back(st):
+        """The host copy _read_back queued last, once its event has completed (nothing else is waited for); None before the first."""
+        if st is None or st.last is None:
+            return None
+        host, ev = st.last
+        ev.synchronize()
+        return host
 
     def grad_norm(self):
         """(total_norm, coef) of the last clipped step: the norm of grad_scale * (the reduced gradient) and the coefficient the
         update multiplied it by.  Read back asynchronously: step() queued a 8-byte copy into pinned memory and an event behind its
         commit kernel, and this waits for that event only - neither it nor step() drains the device.  None before the first
         clipped step.  fp16: the values of a step the overflow guard skipped are meaningless."""
-        cs = self._clip_owner._clip_state
-        if cs is None or cs.last is None:
-            return None
-        host, ev = cs.last
-        ev.synchronize()
-        return float(host[1]), float(host[0])
+        host = self._last_read_back(self._clip_owner._clip_state)
+        return None if host is None else (float(host[1]), float(host[0]))
 
     def _decay_bits(self):
         """The decay map (decay_words of the slot table) on the device, made on first use by the engine that owns flat_g; engines
         built with share= use the owner's."""
-        own = self._clip_owner
-        if own._decay_map is None:
-            words = decay_words(own.slot, own.n_train)
-            own._decay_map = torch.from_numpy(words.view(np.int32)).to(own.dev)
-        return own._decay_map
+        return self._owned("_decay_map", lambda own: torch.from_numpy(decay_words(own.slot, own.n_train).view(np.int32)).to(own.dev))
 
     def _lamb_buffers(self):
         """State of step(lamb=True), made on first use by the engine that owns flat_g (engines built with share= use it, so a
         shared slot table yields ONE chunk table): lamb_chunks of the slot table on the host and on the device, two fp32
         partials per chunk, the trust table (trust, ||w||, ||u|| per tensor) and a pinned ring for its read-back."""
-        own = self._clip_owner
-        if own._lamb_state is None:
+        def make(own):
             names, chunks, tensors = lamb_chunks(own.slot, own.n_train)
             ch, tn = torch.from_numpy(chunks).contiguous(), torch.from_numpy(tensors).contiguous()
             nt = len(names)
-            own._lamb_state = SimpleNamespace(
+            return SimpleNamespace(
                 names=names, chunks_host=ch, tensors_host=tn, chunks=ch.to(own.dev), tensors=tn.to(own.dev), n_chunks=len(chunks),
                 n_tensors=nt, firsts=chunks[:, 0].astype(np.int64), adapted=[i for i in range(nt) if tensors[i, 2]],
                 part=torch.zeros(2 * len(chunks), dtype=torch.float32, device=own.dev),
                 trust=torch.zeros(3 * nt, dtype=torch.float32, device=own.dev),
                 ring=torch.zeros(8, 3 * nt, dtype=torch.float32).pin_memory(), count=0, last=None)
-        return own._lamb_state
+        return self._owned("_lamb_state", make)
 
     def trust_ratios(self):
         """{name: (trust, ||w||, ||u||)} of the adapted tensors (the decay set) at the last step(lamb=True): the ratio the update
@@ -1745,10 +1762,9 @@ class Engine:
         queued a copy into pinned memory and an event behind its last launch, and this waits for that event only.  None before
         the first such step.  fp16: a step the overflow guard skipped leaves the table of the step before it."""
         ls = self._clip_owner._lamb_state
-        if ls is None or ls.last is None:
+        host = self._last_read_back(ls)
+        if host is None:
             return None
-        host, ev = ls.last
-        ev.synchronize()
         nt = ls.n_tensors
         return {ls.names[i]: (float(host[i]), float(host[nt + i]), float(host[2 * nt + i])) for i in ls.adapted}
 
@@ -1756,11 +1772,10 @@ class Engine:
         """The average of flat[True] (step(ema_decay > 0)): fp32, laid out like flat[True], made on first use by the engine that
         owns flat[True] as a copy of the parameters as they are now, on the current stream (the first step with the average on
         calls this before its update); engines built with share= use the owner's."""
-        own = self._clip_owner
-        if own._ema is None:
-            own._ema = own.flat[True].clone()
+        def make(own):
             own.ema_updates = 0
-        return own._ema
+            return own.flat[True].clone()
+        return self._owned("_ema", make)
 
     @property
     def ema_updates(self):
@@ -1860,9 +1875,76 @@ class Engine:
             self.ema_updates = int(osd["ema_updates"])
         self.drop_calls = int(osd["dropout_calls"])
 
+    def _rate_ranges(self, lr, lr_bert, lr_news_head):
+        """[(lo, hi, rate)] over flat[True], a pure function of the slot table and the three rates: the BERT layers at lr_bert, the
+        news encoder's pooling + dense at lr_news_head, the user encoders / transform matrices at lr (None: lr).  Neighbours with
+        one rate are one range, i.e. one launch."""
+        head0 = self.slot[PFX + ("attn.att_fc1.weight" if self.cfg.pooling == "att" else "dense.weight")][1]   # end of the BERT layers
+        _, o, n, _ = self.slot[PFX + "dense.bias"]
+        rest0 = min(_rup(o + n, 64), self.n_train)   # user encoders / transform matrices start here
+        lb = lr if lr_bert is None else lr_bert
+        lh = lr if lr_news_head is None else lr_news_head
+        ranges = []
+        for lo_, hi_, rate in ((0, head0, lb), (head0, rest0, lh), (rest0, self.n_train, lr)):
+            if ranges and ranges[-1][2] == rate and ranges[-1][1] == lo_:
+                ranges[-1] = (ranges[-1][0], hi_, rate)
+            elif hi_ > lo_:
+                ranges.append((lo_, hi_, rate))
+        return ranges
+
+    def _gather(self, sync, guard, stamp, max_grad_norm, grad_scale, lamb_on):
+        """The gather phase of step(): bring in the WHOLE reduced gradient and leave on the device what the update reads of it -
+        the guard word (guard is not None: fp16) and the clip coefficient (max_grad_norm is not None) - before any slice is
+        updated.  Returns the clip state (None without clip).  A sync whose collectives have landed is waited for whole
+        (sync.wait()) in front of the first scan; with collectives in flight each bucket is scanned behind its own wait_bucket, in
+        completion order, so the scans hide under the collectives still in flight.
+        clip: the gradient is ALWAYS scanned slice by slice over bucket_ranges() in that order (tnr_grad_sumsq_scan, which under
+        fp16 is the overflow guard's scan as well), so the coefficient's bits do not depend on whether the step ran
+        data-parallel; then tnr_grad_nonfinite_commit (fp16) and tnr_grad_clip_commit.
+        guard without clip: the whole gradient decides - identically on every rank, since inf / nan survive the all-reduce.
+        Bucketed, tnr_grad_nonfinite_scan per bucket of sync.ranges as given (what lies between buckets are alignment gaps, zero
+        gradients), then the one-thread tnr_grad_nonfinite_commit: only the last bucket's scan, the commit and the update itself
+        (79 us at the headline) stay behind the last collective.  Otherwise the fused tnr_grad_nonfinite over everything.
+        neither (bf16 LAMB; bf16 without a pending sync): the waits alone.
+        Under clip and under LAMB a pending sync's buckets must be bucket_ranges() (the slices of the clip state; the order a
+        tensor's norm may rely on)."""
+        cs = self._clip_buffers() if max_grad_norm is not None else None
+        bucketed = sync is not None and sync.pending
+        if bucketed:
+            if cs is not None:
+                assert [tuple(r) for r in sync.ranges] == [(s_, e_) for s_, e_, _ in cs.slices], "sync buckets are not bucket_ranges()"
+            elif lamb_on:
+                assert [tuple(r) for r in sync.ranges] == [tuple(r) for r in self.bucket_ranges()], "sync buckets are not bucket_ranges()"
+        elif sync is not None:
+            sync.wait()
+        if cs is not None:
+            for b, (s_, e_, off) in enumerate(cs.slices):
+                if bucketed:
+                    sync.wait_bucket(b)
+                T.call("tnr_grad_sumsq_scan", self.flat_g[s_:e_], e_ - s_, cs.part[off:], guard, stamp)
+            if guard is not None:
+                T.call("tnr_grad_nonfinite_commit", guard, stamp)
+            T.call("tnr_grad_clip_commit", cs.part, cs.n_part, float(max_grad_norm), grad_scale, cs.clip)
+        elif bucketed:
+            for b, (s_, e_) in enumerate(sync.ranges):
+                sync.wait_bucket(b)
+                if guard is not None:
+                    T.call("tnr_grad_nonfinite_scan", self.flat_g[s_:e_], e_ - s_, guard, stamp)
+            if guard is not None:
+                T.call("tnr_grad_nonfinite_commit", guard, stamp)
+        elif guard is not None:
+            T.call("tnr_grad_nonfinite", self.flat_g, self.n_train, guard, stamp)
+        return cs
+
     def step(self, lr, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, lr_bert=None, amsgrad=True, lr_news_head=None, sync=None,
              max_grad_norm=None, weight_decay=0.0, warmup_steps=0, lr_decay_steps=0, ema_decay=None, ema_warmup=False, lamb=False):
         """torch.optim.Adam(amsgrad=True).step() (run.py:134,195) + refresh of the 16-bit weight copies.
+        Phases, each written once and run in this order.  Setup: flags, the scaler's poll and stamp, step_count, the schedule's
+        and the average's three candidates, the rate ranges (_rate_ranges).  Gather (_gather): the whole reduced gradient, the
+        guard word and the clip coefficient left on the device.  Update: the Adam family, one launch per rate range, or LAMB
+        (norms, commit, one launch per rate range).  Afterwards: scaler.record, the clip read-back, the trust read-back
+        (_read_back), refresh_shadows.  One mode has no gather: bf16 with collectives in flight and neither clip nor LAMB needs no
+        whole gradient, and its update runs slice by slice behind each wait_bucket, then over what lies outside the buckets.
         lr_bert / lr_news_head: learning rates of the encoder layers / of the news encoder's pooling + dense when they
         differ (PLM-NR/run.py:104-106: {'params': pretrained, 'lr': pretrain_lr}, {'params': rest, 'lr': lr}; the notebooks
         use 1e-6 for bert_model and 1e-5 for the rest).  amsgrad=False: plain Adam (Post-train_KD.ipynb cell 18).
@@ -1871,10 +1953,9 @@ class Engine:
         max_grad_norm > 0: torch.nn.utils.clip_grad_norm_(all trainable parameters, max_grad_norm) on grad_scale * flat_g, i.e.
         AFTER the data-parallel reduction (a clip_grad_norm_ between backward() and step() would see the un-reduced gradient) and
         on the device: ONE norm over everything trainable, whatever the learning-rate ranges.  The gradient is then ALWAYS scanned
-        slice by slice over bucket_ranges() in that order (tnr_grad_sumsq_scan, which under fp16 is the overflow guard's scan as
-        well; with a pending sync each bucket behind its own wait_bucket), so the coefficient's bits do not depend on whether
-        the step ran data-parallel; then tnr_grad_nonfinite_commit (fp16), tnr_grad_clip_commit and the update of every rate range
-        through tnr_amsgrad_step_clipped.  A global norm needs the whole gradient first, so under bf16 this REPLACES the
+        slice by slice over bucket_ranges(), with a pending sync each bucket behind its own wait_bucket (_gather has the call
+        sequence), so the coefficient's bits do not depend on whether the step ran data-parallel; then the update of every rate
+        range through tnr_amsgrad_step_clipped.  A global norm needs the whole gradient first, so under bf16 this REPLACES the
         bucket-by-bucket update: the update waits for the last bucket, as fp16's always does.  grad_norm() reads the result back.
         None or <= 0: off - the calls, kernels, bits and buffers of a step without it.
         weight_decay > 0: torch.optim.AdamW's decoupled decay - p *= 1 - lr_k weight_decay, then the update on the undecayed
@@ -1942,17 +2023,8 @@ class Engine:
             self.ema_updates += 1
             # formed in double, rounded once (by the float argument)
             ema_w = [1.0 - ema_decay_at(max(self.step_count - k, 1) - 1, ema_d, ema_warmup) for k in range(3)]
-        head0 = self.off(PFX + ("attn.att_fc1.weight" if self.cfg.pooling == "att" else "dense.weight"))   # end of the BERT layers
-        e = self.off(PFX + "dense.bias") + self.slot[PFX + "dense.bias"][2]
-        rest0 = min(_rup(e, 64), self.n_train)   # user encoders / transform matrices start here
-        lb = lr if lr_bert is None else lr_bert
-        lh = lr if lr_news_head is None else lr_news_head
-        ranges = []
-        for lo_, hi_, rate in ((0, head0, lb), (head0, rest0, lh), (rest0, self.n_train, lr)):     # neighbours with one rate: one launch
-            if ranges and ranges[-1][2] == rate and ranges[-1][1] == lo_:
-                ranges[-1] = (ranges[-1][0], hi_, rate)
-            elif hi_ > lo_:
-                ranges.append((lo_, hi_, rate))
+        ranges = self._rate_ranges(lr, lr_bert, lr_news_head)
+
         def launch(lo_, hi_, rate):
             if hi_ > lo_:
                 args = (self.flat[True][lo_:hi_], self.flat_g[lo_:hi_], self.adam_m[lo_:hi_], self.adam_v[lo_:hi_],
@@ -1971,33 +2043,23 @@ class Engine:
                 else:
                     T.call("tnr_amsgrad_step_guarded", *args, guard, stamp, sc.skipped)
 
-        if lamb_on:
-            ls = self._lamb_buffers()
-            cs = self._clip_buffers() if clip_on else None
-            bucketed = sync is not None and sync.pending
-            slices = [(s_, e_) for s_, e_, _ in cs.slices] if clip_on else (list(sync.ranges) if bucketed else [])
-            if bucketed:
-                assert [tuple(r) for r in sync.ranges] == [tuple(r) for r in self.bucket_ranges()], "sync buckets are not bucket_ranges()"
-            elif sync is not None:
-                sync.wait()
-            # the whole (reduced) gradient first: every bucket in completion order, scanned as it lands when clip or the guard is on
-            if clip_on:
-                for b, (s_, e_, off) in enumerate(cs.slices):
-                    if bucketed:
-                        sync.wait_bucket(b)
-                    T.call("tnr_grad_sumsq_scan", self.flat_g[s_:e_], e_ - s_, cs.part[off:], guard, stamp)
-                if guard is not None:
-                    T.call("tnr_grad_nonfinite_commit", guard, stamp)
-                T.call("tnr_grad_clip_commit", cs.part, cs.n_part, float(max_grad_norm), grad_scale, cs.clip)
-            elif bucketed:
-                for b, (s_, e_) in enumerate(slices):
-                    sync.wait_bucket(b)
-                    if guard is not None:
-                        T.call("tnr_grad_nonfinite_scan", self.flat_g[s_:e_], e_ - s_, guard, stamp)
-                if guard is not None:
-                    T.call("tnr_grad_nonfinite_commit", guard, stamp)
-            elif guard is not None:
-                T.call("tnr_grad_nonfinite", self.flat_g, self.n_train, guard, stamp)
+        # bf16 with collectives in flight and nothing that needs the whole gradient first: the update itself runs bucket by bucket
+        by_bucket = not (lamb_on or clip_on) and guard is None and sync is not None and bool(sync.pending)
+        ls = self._lamb_buffers() if lamb_on else None
+        cs = None if by_bucket else self._gather(sync, guard, stamp, max_grad_norm if clip_on else None, grad_scale, lamb_on)
+        if by_bucket:
+            done = []
+            for b, (s_, e_) in enumerate(sync.ranges):       # completion order of backward = launch order of the all-reduces
+                sync.wait_bucket(b)
+                for lo_, hi_, rate in ranges:
+                    launch(max(lo_, s_), min(hi_, e_), rate)
+                done.append((s_, e_))
+            pos = 0                                          # anything outside the buckets (alignment gaps: zero gradients)
+            for s_, e_ in sorted(done) + [(self.n_train, self.n_train)]:
+                for lo_, hi_, rate in ranges:
+                    launch(max(lo_, pos), min(hi_, s_), rate)
+                pos = max(pos, e_)
+        elif lamb_on:
             known = sc.skipped if guard is not None else 0
             clip_ = cs.clip if clip_on else None
             vmax_ = self.adam_vmax if amsgrad else None
@@ -2012,78 +2074,13 @@ class Engine:
                            ls.chunks[c0:c1], ls.chunks_host[c0:c1], c1 - c0, ls.n_tensors, self.step_count, rate * mult[0],
                            rate * mult[1], rate * mult[2], beta1, beta2, eps, grad_scale, wd, guard, stamp, known, clip_, ls.trust,
                            ema if ema_on else None, *(ema_w if ema_on else (0.0, 0.0, 0.0)))
-            if guard is not None:
-                sc.record(used)
-            if clip_on:
-                host = cs.ring[cs.count % 8]
-                cs.count += 1
-                host.copy_(cs.clip, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                cs.last = (host, ev)
-            host = ls.ring[ls.count % 8]
-            ls.count += 1
-            host.copy_(ls.trust, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            ls.last = (host, ev)
-        elif clip_on:
-            cs = self._clip_buffers()
-            bucketed = sync is not None and sync.pending
-            if bucketed:
-                assert [tuple(r) for r in sync.ranges] == [(s_, e_) for s_, e_, _ in cs.slices], "sync buckets are not bucket_ranges()"
-            elif sync is not None:
-                sync.wait()
-            for b, (s_, e_, off) in enumerate(cs.slices):
-                if bucketed:
-                    sync.wait_bucket(b)
-                T.call("tnr_grad_sumsq_scan", self.flat_g[s_:e_], e_ - s_, cs.part[off:], guard, stamp)
-            if guard is not None:
-                T.call("tnr_grad_nonfinite_commit", guard, stamp)
-            T.call("tnr_grad_clip_commit", cs.part, cs.n_part, float(max_grad_norm), grad_scale, cs.clip)
-            for lo_, hi_, rate in ranges:
-                launch(lo_, hi_, rate)
-            if guard is not None:
-                sc.record(used)
-            host = cs.ring[cs.count % 8]
-            cs.count += 1
-            host.copy_(cs.clip, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            cs.last = (host, ev)
-        elif guard is not None:
-            # the WHOLE (reduced) gradient decides before any slice is updated - identically on every rank, since inf / nan
-            # survive the all-reduce.  Under data parallelism each bucket is scanned as soon as ITS all-reduce has landed (the
-            # scans hide under the collectives still in flight; what lies between buckets are alignment gaps, zero gradients); only
-            # the last bucket's scan, the one-thread commit and the update itself (79 us at the headline) stay behind the last
-            # collective.  (bf16 has no guard and updates bucket by bucket, below.)
-            if sync is not None and sync.pending:
-                for b, (s_, e_) in enumerate(sync.ranges):
-                    sync.wait_bucket(b)
-                    T.call("tnr_grad_nonfinite_scan", self.flat_g[s_:e_], e_ - s_, guard, stamp)
-                T.call("tnr_grad_nonfinite_commit", guard, stamp)
-            else:
-                if sync is not None:
-                    sync.wait()
-                T.call("tnr_grad_nonfinite", self.flat_g, self.n_train, guard, stamp)
-            for lo_, hi_, rate in ranges:
-                launch(lo_, hi_, rate)
-            sc.record(used)
-        elif sync is not None and sync.pending:
-            done = []
-            for b, (s_, e_) in enumerate(sync.ranges):       # completion order of backward = launch order of the all-reduces
-                sync.wait_bucket(b)
-                for lo_, hi_, rate in ranges:
-                    launch(max(lo_, s_), min(hi_, e_), rate)
-                done.append((s_, e_))
-            pos = 0                                          # anything outside the buckets (alignment gaps: zero gradients)
-            for s_, e_ in sorted(done) + [(self.n_train, self.n_train)]:
-                for lo_, hi_, rate in ranges:
-                    launch(max(lo_, pos), min(hi_, s_), rate)
-                pos = max(pos, e_)
         else:
-            if sync is not None:
-                sync.wait()
             for lo_, hi_, rate in ranges:
                 launch(lo_, hi_, rate)
+        if guard is not None:
+            sc.record(used)
+        if clip_on:
+            self._read_back(cs, cs.clip)
+        if lamb_on:
+            self._read_back(ls, ls.trust)
         self.refresh_shadows(all_layers=False)
