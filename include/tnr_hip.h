@@ -750,6 +750,34 @@ int tnr_topk_scores(const float* users, int64_t u_rs, int64_t Nu, const float* n
                     void* work, int64_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * Rank metrics of the eval path (csrc/evaluate.hip): what the reference computes per impression on the host
+ * (Tiny-NewsRec/run.py:254-262: one dot product per candidate, then roc_auc_score, mrr_score, ndcg_score at 5 and 10).
+ * Impressions are ragged: impression b owns cand / label / scores [offs[b], offs[b + 1]) (offs int32 (B + 1), non-decreasing from
+ * 0); cand holds rows of `news` in [0, Nn) - row 0, the padding news, is scored like any other - and label 0 or 1.  A candidate
+ * outside [0, Nn) is never read and scores NaN.
+ *   Score: s(u, n) = the fp32 fma chain over k = 0, 1, ..., D - 1 from +0 of users[u, k] * news[n, k] - tnr_topk_scores' bits for
+ *   the same pair; they depend on (user row, news row, D) alone, not on the impression, its place in the launch, the strides or
+ *   the width of the loads (16-byte aligned operands with strides % 4 == 0 take 16-byte loads, others scalar ones).
+ *   An impression with P positives and Q = C - P negatives is skipped when P = 0 or Q = 0 (C = 0 included).
+ *   Position of a positive i: r_i = #{j : s_j > s_i} + #{j > i : s_j == s_i} (float compares: among equal scores the later index
+ *   ranks first, +0 == -0).  In double:
+ *     AUC    = sum over positives of (#negatives s_j < s_i + 0.5 #negatives s_j == s_i) / (P Q)
+ *     MRR    = (sum over positives of 1 / (r_i + 1)) / P
+ *     nDCG@k = (sum over positives with r_i < k of 1 / log2(r_i + 2)) / (sum over t < min(P, k) of 1 / log2(t + 2))
+ * scores (offs[B] floats, required) receives every candidate's score and is read back by the rank phase, so an impression may
+ * have any number of candidates.  per (B, 4) doubles or NULL: AUC, MRR, nDCG@5, nDCG@10 of each impression, zeros where it is
+ * skipped; an impression's values do not depend on its place in the launch.  acc[6] = {impressions seen, impressions scored,
+ * sum AUC, sum MRR, sum nDCG@5, sum nDCG@10}: accumulate = 0 overwrites it, 1 adds this launch's totals.  The totals are summed
+ * in a fixed order in double by one workgroup - no float atomics, bit-identical from run to run.  Without `per` that workgroup
+ * also has to compute every impression's values again from `scores` (same bits, one CU's speed): pass `per` where time matters.
+ * No allocation, no host synchronisation.  B = 0 launches the totals alone (accumulate = 0 zeroes acc) and needs only acc.
+ * Limits: 1 <= D <= 1024, strides >= D, B and Nn below 2^31, acc and per 8-byte aligned.  Anything else or a null required
+ * pointer launches nothing, writes nothing and returns TNR_EINVAL. */
+int tnr_rank_metrics(const float* users, int64_t u_rs, int64_t B, const float* news, int64_t n_rs, int64_t Nn, int D,
+                     const int32_t* offs, const int32_t* cand, const int32_t* label, float* scores, double* per, double* acc,
+                     int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Collectives of the data-parallel step.  Replace hvd.init / hvd.broadcast_parameters /
  * hvd.broadcast_optimizer_state (Tiny-NewsRec/run.py:141-144, utils.py:43-60) and the gradient all-reduce inside
  * hvd.DistributedOptimizer (run.py:145-149: average of the trainable parameters' gradients, fp32, no compression).

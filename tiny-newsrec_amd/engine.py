@@ -228,6 +228,31 @@ class _ReduceBatch:
                 T.call("tnr_reduce_multi", t[0], t[1])
 
 
+def pack_impressions(cands, labels):
+    """The eval loader's per-impression arrays as tnr_rank_metrics takes them -> (cand int32, label int32, offs int32 (B + 1)):
+    impression b owns [offs[b], offs[b + 1]) of cand and label.  Host only.  Refused: a label other than 0 or 1, a negative
+    candidate index, unlike lengths, more candidates than int32 offsets hold."""
+    n = len(cands)
+    if len(labels) != n:
+        raise ValueError("pack_impressions: %d candidate arrays, %d label arrays" % (n, len(labels)))
+    cs = [np.asarray(c).reshape(-1) for c in cands]
+    ys = [np.asarray(y).reshape(-1) for y in labels]
+    for b, (c, y) in enumerate(zip(cs, ys)):
+        if c.size != y.size:
+            raise ValueError("pack_impressions: impression %d has %d candidates and %d labels" % (b, c.size, y.size))
+    offs = np.zeros(n + 1, np.int64)
+    np.cumsum([c.size for c in cs], out=offs[1:])
+    if offs[-1] >= 2 ** 31:
+        raise ValueError("pack_impressions: %d candidates do not fit int32 offsets" % offs[-1])
+    cand = np.concatenate(cs) if offs[-1] else np.zeros(0, np.int64)
+    label = np.concatenate(ys) if offs[-1] else np.zeros(0, np.int64)
+    if cand.size and (cand.min() < 0 or cand.max() >= 2 ** 31):
+        raise ValueError("pack_impressions: candidate index %d outside [0, 2^31)" % (cand.min() if cand.min() < 0 else cand.max()))
+    if not ((label == 0) | (label == 1)).all():
+        raise ValueError("pack_impressions: labels must be 0 or 1, found %s" % label[(label != 0) & (label != 1)][0])
+    return cand.astype(np.int32), label.astype(np.int32), offs.astype(np.int32)
+
+
 def lr_schedule(u, warmup_steps=0, lr_decay_steps=0):
     """Multiplier of every learning rate at an update that `u` updates precede (step(warmup_steps=W, lr_decay_steps=T)):
     u / W while u < W (the first update has rate 0), then max(0, (T - u) / max(1, T - W)) if T > 0 and 1 if T == 0 -
@@ -1107,6 +1132,50 @@ class Engine:
         B <= the engine's batch; every buffer and counter is left as user_vectors leaves it."""
         users = self.user_vectors(news_scoring, hist_idx, history_mask)
         return self.topk(users, news_scoring, k, exclude=hist_idx if exclude_history else None, first_row=1)
+
+    @torch.no_grad()
+    def rank_metrics(self, users, news_scoring, cands, labels, acc=None, per=False, offs=None):
+        """AUC, MRR, nDCG@5 and nDCG@10 of a batch of impressions on the device (tnr_rank_metrics, include/tnr_hip.h): row b of
+        users (B, D) against the rows of news_scoring (Nn, D) that impression b lists, with run.test's skip rule (no positive or
+        no negative) and metrics.py's tie rule.  cands / labels: the eval loader's lists of numpy arrays, packed by
+        pack_impressions and uploaded in one copy - or int32 device tensors already packed, with offs (B + 1) beside them.
+        acc: a float64 (6,) device tensor {seen, scored, sum AUC, sum MRR, sum nDCG@5, sum nDCG@10} to add this batch's totals
+        to; None starts a new one.  -> (acc, scores fp32 (all candidates), per (B, 4) float64 or None).  Nothing is read back."""
+        assert users.dtype == torch.float32 and news_scoring.dtype == torch.float32 and users.dim() == 2 and news_scoring.dim() == 2
+        assert users.shape[1] == news_scoring.shape[1] and users.stride(1) == 1 and news_scoring.stride(1) == 1
+        B, D = users.shape
+        Nn = news_scoring.shape[0]
+        dev = users.device
+        if isinstance(cands, torch.Tensor):
+            assert offs is not None and offs.numel() == B + 1, "packed impressions come with their offsets"
+            cand, label, offs = (x.to(device=dev, dtype=torch.int32).contiguous() for x in (cands, labels, offs))
+            assert cand.numel() == label.numel()
+        else:
+            assert len(cands) == B and len(labels) == B
+            c, y, o = pack_impressions(cands, labels)
+            if c.size and int(c.max()) >= Nn:
+                raise ValueError("rank_metrics: candidate row %d outside the %d rows of news_scoring" % (int(c.max()), Nn))
+            buf = torch.from_numpy(np.concatenate([o, c, y])).to(dev)          # the batch's one upload
+            offs, cand, label = buf[:B + 1], buf[B + 1:B + 1 + c.size], buf[B + 1 + c.size:]
+        n_cand = cand.numel()
+        if n_cand == 0:                                                        # impressions without candidates: nothing is indexed,
+            cand = label = torch.zeros((1,), device=dev, dtype=torch.int32)    # but the library refuses a null pointer
+        scores = torch.empty((max(n_cand, 1),), device=dev, dtype=torch.float32)
+        per_t = torch.empty((max(B, 1), 4), device=dev, dtype=torch.float64)   # always: the kernel's fast form keeps them there
+        accumulate = acc is not None
+        if acc is None:
+            acc = torch.empty((6,), device=dev, dtype=torch.float64)
+        assert acc.dtype == torch.float64 and acc.numel() == 6 and acc.is_contiguous() and acc.device == scores.device
+        T.call("tnr_rank_metrics", users, users.stride(0), B, news_scoring, news_scoring.stride(0), Nn, D, offs, cand, label, scores,
+               per_t, acc, 1 if accumulate else 0)
+        return acc, scores[:n_cand], (per_t[:B] if per else None)
+
+    @torch.no_grad()
+    def evaluate(self, news_scoring, hist_idx, history_mask, cands, labels, acc=None, per=False):
+        """user_vectors(...) followed by rank_metrics over each impression's candidates: one batch of run.test's loop without
+        the host.  B <= the engine's batch; every buffer and counter is left as user_vectors leaves it."""
+        users = self.user_vectors(news_scoring, hist_idx, history_mask)
+        return self.rank_metrics(users, news_scoring, cands, labels, acc=acc, per=per)
 
     def _prepare(self, B):
         # buffers are sized for the exact batch: row strides of the stacked (T, Rt, D) arrays and the

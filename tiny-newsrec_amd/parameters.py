@@ -51,6 +51,10 @@ def _flag_table():
           ("top_k", _positive_int, 10, dict(help="--mode recommend: news per user, 1..128 (the fused score-and-select kernel's limit)")),
           ("recommend_out", str, None, dict(help="--mode recommend: the output file, one line per behaviours line in file order, `impression_id \\t user_id \\t nid:score nid:score ...` best first; with more than one rank, rank r writes PATH.r for its shard; default <model_dir>/recommend.tsv")),
           ("exclude_history", _B, True, dict(help="--mode recommend: never recommend a news the user's history already holds")),
+          ("device_metrics", _B, False, dict(help="--mode test: score each impression's candidates and compute AUC / MRR / nDCG@5 / nDCG@10 on the device (one kernel call per batch, totals kept in double in a fixed order, no host copy of the news vectors) instead of the reference's per-impression numpy loop; the same skip rule, tie rule and log lines; the scores are the kernel's own fp32 fma chains, so near-ties may rank differently from the host's BLAS dot products; off = the reference's host loop")),
+          ("valid_data_dir", str, None, dict(help="--mode train: a directory laid out like --test_data_dir (news.tsv + behaviours files) to validate on: at the end of every epoch, before the checkpoint is written, and every --valid_steps batches, its news are encoded by the live student and its impressions ranked on the device (the --device_metrics path, sharded over the workers and all-reduced as --mode test does). The four metrics are logged, the epoch checkpoint gains `valid`, and whenever AUC improves on the run's best <model_dir>/best.pt is written (the model keys and `valid`, no optimiser state). Training itself computes the same bits with or without it; unset = off (the reference has no validation)")),
+          ("valid_steps", int, 0, dict(help="with --valid_data_dir: also validate after every batch whose 1-based count in the epoch is a multiple of this; must be a multiple of --grad_accum_steps, so that validation never falls inside an accumulation window; 0 = at epoch ends only")),
+          ("valid_filename_pat", str, "behaviors_*.tsv", dict(help="with --valid_data_dir: the behaviours files to validate on")),
           ("grad_accum_steps", _positive_int, 1, dict(help="gradient accumulation: one optimiser update per grad_accum_steps batches of --batch_size, on the mean of their gradients (summed on the device in fp32), i.e. an effective batch of grad_accum_steps * batch_size * world impressions; --warmup_steps, --lr_decay_steps and --ema_warmup count updates, not batches; under data parallelism one gradient all-reduce per update, started in the window's last backward (DistributedDataParallel's no_sync for the others); a partial window at the end of an epoch is dropped; an fp16 overflow in any of the batches skips the whole update; 1 = off (the reference updates after every batch)")),
           ("save_optimizer", _B, False, dict(help="the epoch checkpoint also holds optimizer_state_dict (Adam's moments per trainable key, the updates taken - the position of --warmup_steps / --lr_decay_steps / --ema_warmup -, the fp16 loss scaler, the average's update count, the dropout call counter: 12 bytes per trainable element) and train_state (epoch, updates, the flags it ran with); off = the reference's checkpoint keys")),
           ("resume", _B, False, dict(help="with --load_ckpt_name: continue the run that wrote that checkpoint with --save_optimizer True - the optimiser state is restored after the parameters (and the average), the epoch loop and the file-fed loader's shard / shuffle seeds go on at the saved epoch - bit for bit what the uninterrupted run computes; flags that differ from the saved ones are logged as a warning. Off, --load_ckpt_name restores the parameters (and the average) only and --start_epoch is what it was")),
@@ -81,6 +85,15 @@ def check_args(args):
     """Flag combinations that cannot run, refused before anything is built."""
     if getattr(args, "resume", False) and not getattr(args, "load_ckpt_name", None):
         raise ValueError("--resume True needs --load_ckpt_name (the checkpoint a --save_optimizer True run wrote)")
+    valid_steps = getattr(args, "valid_steps", 0) or 0
+    if valid_steps < 0:
+        raise ValueError("--valid_steps must be 0 (epoch ends only) or positive, got %d" % valid_steps)
+    if valid_steps and not getattr(args, "valid_data_dir", None):
+        raise ValueError("--valid_steps %d needs --valid_data_dir (the held-out set to validate on)" % valid_steps)
+    accum = getattr(args, "grad_accum_steps", 1) or 1
+    if valid_steps % accum:
+        raise ValueError("--valid_steps %d is no multiple of --grad_accum_steps %d: validation would fall inside an accumulation "
+                         "window" % (valid_steps, accum))
 
 
 def parse_args(argv=None):

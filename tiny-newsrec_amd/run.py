@@ -187,12 +187,36 @@ def train(args):
     if args.cache_frozen_layers and dev_news is not None and eng.build_frozen_cache(dev_news):
         logging.info("[%d] frozen layers 0..%d cached for %d news (%.2f GB)" % (
             rank, eng.lo - 1, dev_news.shape[0], eng.fcache[0].numel() * 4 / 1e9))
+    valid = _Validation(args, size, rank, local) if getattr(args, "valid_data_dir", None) else None
+    valid_steps = getattr(args, "valid_steps", 0) if valid is not None else 0
+
+    def model_ckpt():
+        """The epoch checkpoint's model keys (run.py:205-214, plus the average of an --ema_decay run)."""
+        ck = {"model_state_dict": {k: v.cpu() for k, v in model.state_dict().items()},
+              "category_dict": category_dict, "word_dict": None, "subcategory_dict": subcategory_dict}
+        esd = model.ema_state_dict() if args.ema_decay > 0 else None
+        if esd is not None:          # --ema_decay: the averaged model beside the trained one, which stays what the reference loads
+            ck["ema_state_dict"] = {k: v.cpu() for k, v in esd.items()}
+            ck["ema"] = {"decay": args.ema_decay, "warmup": bool(args.ema_warmup), "updates": eng.ema_updates}
+        return ck
+
+    def validate(epoch, batch):
+        """Every rank: the held-out metrics of the weights as they are now; rank 0 keeps the best of the run in best.pt."""
+        v = valid.run(eng, epoch, batch)
+        if rank == 0 and valid.improved(v):
+            os.makedirs(args.model_dir, exist_ok=True)
+            best_path = os.path.join(args.model_dir, "best.pt")
+            torch.save(dict(model_ckpt(), valid=v), best_path)
+            logging.info(f"Best validation AUC so far: model saved to {best_path}")
+        return v
+
     logging.info("Training...")
     for ep in range(first_epoch, args.epochs):
         loss_sum, acc_sum, t0 = torch.zeros((), device="cuda"), torch.zeros((), device="cuda"), time.time()
         if not args.synthetic:
             steps_cap = epoch_cap()
         optimizer.reset_window()         # --grad_accum_steps: a window never spans two epochs
+        n_batches, last_valid = 0, None
         left_over = min(args.max_steps_per_epoch + 1, steps_cap) % args.grad_accum_steps
         if left_over and not accum_logged:
             accum_logged = True
@@ -234,18 +258,21 @@ def train(args):
                     ", grad norm {:g} (clip x{:.3g})".format(*gn) if gn is not None else "",
                     # the host's schedule multiplier of the last step (the device may be up to two skipped steps behind it)
                     ", lr x{:.4g}".format(eng.lr_scale) if eng.lr_scale is not None else ""))
+            n_batches = cnt + 1
+            if valid_steps and n_batches % valid_steps == 0:     # a multiple of --grad_accum_steps: behind an update, never inside a window
+                last_valid = validate(ep + 1, n_batches)
         print(ep + 1)
         if eng.scaler.enabled:
             eng.scaler.drain(eng)        # the epoch's last two overflow answers, before the step count goes into a log line or a file
+        if valid is not None:            # every rank, before the checkpoint; the epoch's last batch may just have been validated
+            if last_valid is None or last_valid["batch"] != n_batches:
+                last_valid = validate(ep + 1, n_batches)
         if rank == 0:                                                        # run.py:205-214
             os.makedirs(args.model_dir, exist_ok=True)
             ckpt_path = os.path.join(args.model_dir, f"epoch-{ep + 1}.pt")
-            ckpt = {"model_state_dict": {k: v.cpu() for k, v in model.state_dict().items()},
-                    "category_dict": category_dict, "word_dict": None, "subcategory_dict": subcategory_dict}
-            esd = model.ema_state_dict() if args.ema_decay > 0 else None
-            if esd is not None:          # --ema_decay: the averaged model beside the trained one, which stays what the reference loads
-                ckpt["ema_state_dict"] = {k: v.cpu() for k, v in esd.items()}
-                ckpt["ema"] = {"decay": args.ema_decay, "warmup": bool(args.ema_warmup), "updates": eng.ema_updates}
+            ckpt = model_ckpt()
+            if valid is not None:
+                ckpt["valid"] = dict(last_valid, updates=eng.step_count)
             if args.save_optimizer:      # what --resume True continues from (after the drain above: the counts are final)
                 optimizer.reset_window()     # a partial window at the end of the epoch is dropped, as the next epoch's start drops it
                 ckpt["optimizer_state_dict"] = optimizer.state_dict()
@@ -283,6 +310,47 @@ def _forward_engine(args, n_layers, sd, add_prefix=""):
     return eng
 
 
+class _Validation:
+    """--valid_data_dir: the held-out set of a training run.  Its news table is read and uploaded once; run() encodes it with the
+    live student through the training engine's own encode_news (the frozen-layer cache is keyed by the training table's address,
+    so this table never hits it, and a forward-only pass leaves nothing behind that a training step reads), takes the user
+    vectors from its user_vectors and the metrics from the device path of test mode, sharded over the ranks by DataLoaderTest
+    and reduced as test() reduces them."""
+
+    def __init__(self, args, size, rank, local):
+        self.args, self.size, self.rank, self.local = args, size, rank, local
+        self.news_index, comb = _news_table(args, args.valid_data_dir, "test")
+        self.dev_news = torch.from_numpy(comb).cuda()
+        self.best = None
+        logging.info("[{}] validation on {}: {} news".format(rank, args.valid_data_dir, comb.shape[0]))
+
+    def run(self, eng, epoch, batch):
+        """-> the `valid` record of the checkpoints; the same on every rank."""
+        from dataloader import DataLoaderTest
+        args = self.args
+        news_scoring = eng.encode_news(self.dev_news)
+        loader = DataLoaderTest(news_index=self.news_index, data_dir=args.valid_data_dir,
+                                filename_pat=getattr(args, "valid_filename_pat", "behaviors_*.tsv"), args=args, world_size=self.size,
+                                worker_rank=self.rank, cuda_device_idx=self.local, enable_prefetch=True, enable_shuffle=False,
+                                enable_gpu=True)
+        sums, n_local, scored = _impression_loop(eng, news_scoring, loader, self.rank, args.log_steps, device_metrics=True)
+        t = _reduce_metrics(sums, n_local, self.size, extra=(scored,))
+        if t[0] == 0:
+            raise ValueError(f"--valid_data_dir {args.valid_data_dir}: no impressions match {getattr(args, 'valid_filename_pat', None)}")
+        m = t[1:5] / t[0]                # by the SAMPLE count, as test mode's final line (run.py:377-379)
+        v = {"auc": float(m[0]), "mrr": float(m[1]), "ndcg5": float(m[2]), "ndcg10": float(m[3]), "seen": int(t[0]),
+             "scored": int(t[5]), "epoch": epoch, "batch": batch, "updates": eng.step_count}
+        logging.info("[{}] Valid: epoch {} batch {}: {} ({} impressions, {} scored)".format(
+            self.rank, epoch, batch, "\t".join("{:0.2f}".format(x * 100) for x in m), v["seen"], v["scored"]))
+        return v
+
+    def improved(self, v):
+        if self.best is not None and not v["auc"] > self.best:
+            return False
+        self.best = v["auc"]
+        return True
+
+
 def get_teacher_emb(args):
     """run.py:382-460: every train news through each teacher's news encoder -> pickled (n+1, D) float32 tables."""
     utils.init_hvd_cuda(False, args.enable_gpu)
@@ -307,7 +375,6 @@ def test(args, collect=None):
     the quality tests compare the per-impression rankings with the reference's."""
     import dist
     from dataloader import DataLoaderTest
-    from metrics import mrr_score, ndcg_score, roc_auc_score
     size, rank, local = utils.init_hvd_cuda(args.enable_hvd, args.enable_gpu)
     ckpt_path = utils.get_checkpoint(args.model_dir, args.load_ckpt_name) if args.load_ckpt_name else utils.latest_checkpoint(args.model_dir)
     assert ckpt_path is not None, "No ckpt found"
@@ -322,13 +389,52 @@ def test(args, collect=None):
     logging.info(f"Model loaded from {ckpt_path}" + (" (the EMA of the weights)" if getattr(args, "use_ema", False) else ""))
     news_index, news_combined = _news_table(args, args.test_data_dir, "test")
     news_scoring = eng.encode_news(torch.from_numpy(news_combined).cuda())
-    scoring_host = news_scoring.cpu().numpy()
-    logging.info("news scoring num: {}".format(scoring_host.shape[0]))
+    logging.info("news scoring num: {}".format(news_scoring.shape[0]))
     loader = DataLoaderTest(news_index=news_index, data_dir=args.test_data_dir, filename_pat=args.filename_pat, args=args,
                             world_size=size, worker_rank=rank, cuda_device_idx=local, enable_prefetch=True,
                             enable_shuffle=False, enable_gpu=True)
-    sums, n_local = np.zeros(4), 0
-    cnt_metric = 0
+    sums, n_local, cnt_metric = _impression_loop(eng, news_scoring, loader, rank, args.log_steps,
+                                                 getattr(args, "device_metrics", False), collect)
+    logging.info("[{}] local_sample_num: {}".format(rank, n_local))
+    t = _reduce_metrics(sums, n_local, size)
+    if rank == 0:
+        # the reference divides the metric sums by the SAMPLE count (run.py:377-379), impressions skipped above included
+        logging.info("[{}] Ed: {}: {}".format(rank, int(t[0]), "\t".join("{:0.2f}".format(x * 100) for x in t[1:5] / t[0])))
+    return sums, n_local, cnt_metric
+
+
+def _impression_loop(eng, news_scoring, loader, rank, log_steps, device_metrics=False, collect=None):
+    """The impression loop of test mode (run.py:332-366) over one pass of an eval loader, which it joins
+    -> (sums of AUC / MRR / nDCG@5 / nDCG@10 over the impressions scored, impressions seen, impressions scored), this rank's.
+    Host form (the reference's): user vectors to the host, per impression one numpy dot product per candidate and metrics.py.
+    device_metrics: one Engine.evaluate per batch adds to six doubles on the device, read back for a log line and at the end -
+    no host copy of news_scoring, no per-impression host work.  collect receives (scores, labels) per impression in file order:
+    the host's dot products, or the device's own scores."""
+    sums, n_local, cnt_metric = np.zeros(4), 0, 0
+    if device_metrics:
+        acc = torch.zeros(6, dtype=torch.float64, device=news_scoring.device)
+        for cnt, (h, m, cands, labels) in enumerate(loader):
+            # a training engine's workspace follows its last batch, which may have been a short one
+            step = min(h.shape[0], eng.B_alloc)
+            for s0 in range(0, h.shape[0], step):
+                _, scores, _ = eng.evaluate(news_scoring, h[s0:s0 + step], m[s0:s0 + step], cands[s0:s0 + step],
+                                            labels[s0:s0 + step], acc=acc)
+                if collect is not None:
+                    s, o = scores.cpu().numpy(), 0
+                    for c, y in zip(cands[s0:s0 + step], labels[s0:s0 + step]):
+                        collect.append((s[o:o + len(c)], y))
+                        o += len(c)
+            n_local += h.shape[0]
+            if cnt % log_steps == 0:
+                a = acc.cpu().numpy()
+                if a[1]:
+                    logging.info("[{}] Ed: {}: {}".format(rank, n_local, "\t".join("{:0.2f}".format(x * 100) for x in a[2:] / a[1])))
+        loader.join()
+        a = acc.cpu().numpy()
+        assert int(a[0]) == n_local, (a[0], n_local)
+        return a[2:].copy(), n_local, int(a[1])
+    from metrics import mrr_score, ndcg_score, roc_auc_score
+    scoring_host = news_scoring.cpu().numpy()
     for cnt, (h, m, cands, labels) in enumerate(loader):
         n_local += h.shape[0]
         users = eng.user_vectors(news_scoring, h, m).cpu().numpy()
@@ -340,18 +446,19 @@ def test(args, collect=None):
             score = scoring_host[c] @ u
             sums += [roc_auc_score(y, score), mrr_score(y, score), ndcg_score(y, score, 5), ndcg_score(y, score, 10)]
             cnt_metric += 1
-        if cnt % args.log_steps == 0 and cnt_metric:
+        if cnt % log_steps == 0 and cnt_metric:
             logging.info("[{}] Ed: {}: {}".format(rank, n_local, "\t".join("{:0.2f}".format(x * 100) for x in sums / cnt_metric)))
     loader.join()
-    logging.info("[{}] local_sample_num: {}".format(rank, n_local))
-    tot = torch.tensor([float(n_local)] + list(sums), dtype=torch.float64, device="cuda")
-    if size > 1:
-        torch.distributed.all_reduce(tot)                                               # hvd.allreduce(Sum), run.py:372-376
-    if rank == 0:
-        t = tot.cpu().numpy()
-        # the reference divides the metric sums by the SAMPLE count (run.py:377-379), impressions skipped above included
-        logging.info("[{}] Ed: {}: {}".format(rank, int(t[0]), "\t".join("{:0.2f}".format(x * 100) for x in t[1:] / t[0])))
     return sums, n_local, cnt_metric
+
+
+def _reduce_metrics(sums, n_local, size, extra=()):
+    """test mode's scalar all-reduce (hvd.allreduce(Sum), run.py:372-376): [samples, the four sums, extra...] over the ranks, as
+    float64 on the host - every rank gets the same numbers."""
+    tot = torch.tensor([float(n_local)] + list(sums) + [float(x) for x in extra], dtype=torch.float64, device="cuda")
+    if size > 1:
+        torch.distributed.all_reduce(tot)
+    return tot.cpu().numpy()
 
 
 def recommend(args):
