@@ -67,31 +67,61 @@ def run_stage1(out_path, dtype, B, n_steps):
         torch.distributed.destroy_process_group()
 
 
-def run(out_path, dtype, B, n_steps):
+def run(out_path, dtype, B, n_steps, opts=None):
+    """opts (optional, a JSON object): "engine" - further EngineConfig keywords (train_embeddings, vocab, max_pos; the weights
+    are then hash-initialised over the engine's own shapes and the news table drawn from its vocabulary), "step" - further
+    Engine.step keywords.  With it the dump also holds the parameters before the first step, the bucket indices the hook was
+    called with, whether each backward's last call launched the last bucket behind the embedding scatter-sum, and grad_norm()
+    of every step.  Without it nothing changes."""
     import dist as D
     import engine as E
     import hashinit
     import synth
+    import tnr_hip as T
     from schema import FULL, state_shapes
     world, rank, _ = D.init("gloo")
     dev = "cuda:0"
     torch.cuda.set_device(0)
     nl, T_, n_news = 2, 2, 3000
-    cfg = E.EngineConfig(n_layers=nl, trainable_layers=(0, 1), num_teachers=T_)
+    ekw, skw = (opts or {}).get("engine", {}), (opts or {}).get("step", {})
+    cfg = E.EngineConfig(n_layers=nl, trainable_layers=(0, 1), num_teachers=T_, **ekw)
     b = B // world
     eng = E.Engine(cfg, dev, max_batch=b, dtype=dtype)
-    eng.load_state_dict(hashinit.init_state_dict(7, state_shapes(FULL, nl, cfg.D, T_)))
+    if opts is None:
+        eng.load_state_dict(hashinit.init_state_dict(7, state_shapes(FULL, nl, cfg.D, T_)))
+    else:
+        eng.load_state_dict(hashinit.init_state_dict(7, eng.shapes))
     D.broadcast_flat([eng.flat[True], eng.flat[False]])
     eng.refresh_shadows(all_layers=True)
     gs = D.GradSync(eng.flat_g, eng.bucket_ranges(), world, force=True)
     d = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    comb, tabs = d(synth.news_table(7, n_news, cfg.L)), d(synth.teacher_tables(7, T_, n_news, cfg.D))
+    comb = d(synth.news_table(7, n_news, cfg.L) if opts is None else synth.news_table(7, n_news, cfg.L, vocab=cfg.vocab))
+    tabs = d(synth.teacher_tables(7, T_, n_news, cfg.D))
     hidx, mask, cidx, label = [d(x) for x in synth.impressions(8, B * n_steps, n_news, cfg.U, cfg.C)]
-    grads = []
+    grads, more = [], {}
+    hook = gs.launch
+    if opts is not None:
+        more.update(params0=eng.flat[True].cpu().numpy(), launched=[], embed_then_last_launch=[], clip=[],
+                    n_buckets=np.int64(len(gs.ranges)), emb_end=np.int64(eng.bucket_ranges()[-1][1]))
+        events, real = [], T.call
+
+        def recorder(name, *a):
+            events.append(name)
+            return real(name, *a)
+
+        def hook(bkt):
+            events.append(bkt)
+            more["launched"].append(bkt)
+            gs.launch(bkt)
+        T.call = recorder
     for st in range(n_steps):
         s = slice(st * B + rank * b, st * B + (rank + 1) * b)
         eng.forward_indexed(comb, hidx[s], mask[s], cidx[s], label[s], tabs)
-        eng.backward(after_bucket=gs.launch if world > 1 else None)
+        if opts is not None:
+            del events[:]
+        eng.backward(after_bucket=hook if world > 1 else None)
+        if opts is not None and world > 1:
+            more["embed_then_last_launch"].append("tnr_scatter_sum_rows" in events and events[-1] == len(gs.ranges) - 1)
         if world > 1:
             assert sorted(gs.pending) == list(range(len(gs.ranges)))      # every bucket's collective is in flight
         if st == 0:
@@ -99,18 +129,25 @@ def run(out_path, dtype, B, n_steps):
             # bucket-by-bucket path of run.py / bench.py
             gs.wait()
             grads.append((eng.flat_g * gs.scale).cpu().numpy().copy())
-            eng.step(lr=1e-4, grad_scale=gs.scale)
+            eng.step(lr=1e-4, grad_scale=gs.scale, **skw)
         else:
-            eng.step(lr=1e-4, grad_scale=gs.scale, sync=gs)
+            eng.step(lr=1e-4, grad_scale=gs.scale, sync=gs, **skw)
             assert not gs.pending
             grads.append((eng.flat_g * gs.scale).cpu().numpy().copy())
+        if "max_grad_norm" in skw:
+            more["clip"].append(eng.grad_norm())
     torch.cuda.synchronize()
     np.savez(out_path % rank, grads=np.stack(grads), params=eng.flat[True].cpu().numpy(), gscale=np.float32(eng.gscale),
-             head0=np.int64(eng.off(E.PFX + "dense.weight")))
+             head0=np.int64(eng.off(E.PFX + "dense.weight")), **{k: np.asarray(v) for k, v in more.items()})
     D.barrier()
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":
-    (run_stage1 if len(sys.argv) > 5 and sys.argv[5] == "stage1" else run)(sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4]))
+    if len(sys.argv) > 6:                   # stage 2 with options (the module docstring's argument list, then a JSON object)
+        import json
+        assert sys.argv[5] == "stage2"
+        run(sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), json.loads(sys.argv[6]))
+    else:
+        (run_stage1 if len(sys.argv) > 5 and sys.argv[5] == "stage1" else run)(sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4]))
