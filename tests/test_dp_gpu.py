@@ -69,6 +69,20 @@ def test_stage1_two_ranks_equal_one_rank_with_the_concatenated_batch(tmp_path):
     assert dp.mean() < 0.02 * 1e-5 and dp.max() <= 2.05 * 1e-5 * steps
 
 
+def test_two_ranks_through_a_schedule_of_unlike_steps(tmp_path):
+    """tests/workers/dp_rank.py, mode "history" (run_history has the rule): one long-lived Engine and GradSync per rank through
+    full -> short -> full -> the loss scale at 0.5 -> back at 1.0, fp16 over gloo, every step against a fresh Engine + GradSync
+    loaded from state_dict() / optimizer_state_dict() - reduced gradient, parameters and all three moment buffers torch.equal, no
+    collective left pending.  Here: neither rank saw a mismatch, every step moved the parameters, both ranks end on identical
+    parameters and the overflow guard counted no skip."""
+    two = _launch(tmp_path, 2, "fp16", 6, 5, "hist", 29631, "history")
+    for r, z in enumerate(two):
+        assert int(z["mismatches"]) == 0, "rank %d: %s" % (r, "; ".join(str(m) for m in z["messages"]))
+        assert z["moved"].all() and len(z["moved"]) == 5 and int(z["steps"]) == 5
+        assert int(z["skipped"]) == 0 and float(z["mult"]) == 1.0
+    assert np.array_equal(two[0]["params"], two[1]["params"]) and np.isfinite(two[0]["params"]).all()
+
+
 class _FakeSync:
     """A GradSync whose collectives are already complete: Engine.step(sync=...) must take the bucket-by-bucket path."""
 

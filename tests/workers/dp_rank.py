@@ -6,7 +6,9 @@ bucketed all-reduce launched from the backward's after_bucket hook exactly as ru
 1/W scale THROUGH Engine.step(sync=...) -- bucket by bucket, each optimiser slice behind its own in-flight collective
 (GradSync keeps the gloo all-reduces asynchronous on pinned host mirrors) -- and dumps its summed gradient and its parameters.
 mode "stage1": the same for post_train_kd.py's step (Stage1Engine: title pass writes the gradients, body pass accumulates and
-fires the buckets)."""
+fires the buckets).
+mode "history": one long-lived Engine and one long-lived GradSync per rank through unlike steps of tests/history_ref.py, every
+step against a fresh Engine + GradSync over the same process group (run_history)."""
 import os
 import sys
 
@@ -144,8 +146,81 @@ def run(out_path, dtype, B, n_steps, opts=None):
         torch.distributed.destroy_process_group()
 
 
+def run_history(out_path, dtype):
+    """Step-history independence at two real ranks: history_ref's model and feeds, rank r takes impressions [r b, (r + 1) b) of each
+    feed (b = 3 of the full batch's 6, 2 of the short one's 4).  ONE Engine and ONE GradSync live through full_a -> short_a (the
+    workspace re-laid, the pinned mirrors kept) -> full_b -> full_a at scaler.mult 0.5 -> full_a at 1.0; every backward launches its
+    buckets through gs.launch, every optimiser step is step(sync=gs).  In front of each step the rank takes state_dict() and
+    optimizer_state_dict(); behind it a FRESH Engine(max_batch=b) with a fresh GradSync is loaded from both and runs the same step
+    over the same process group (both ranks in the same order, so the collectives pair up).  flat_g (the reduced gradient),
+    flat[True], adam_m, adam_v and adam_vmax of the two must be torch.equal - a sum of two ranks is commutative, the collective
+    adds no freedom - and no collective may be left pending.  Mismatches are collected and dumped (a rank that stopped at the first
+    one would leave its peer waiting inside a collective); the parent asserts there are none."""
+    sys.path.insert(0, ROOT)                # history_ref imports the oracle package
+    import dist as D
+    import engine as E
+    import history_ref as HR
+    world, rank, _ = D.init("gloo")
+    assert world == 2
+    dev = "cuda:0"
+    torch.cuda.set_device(0)
+    d = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    P = {k: d(v) for k, v in HR.weights().items()}
+    comb, tabs = d(HR.news()), d(HR.teachers())
+    per = {HR.B_FULL: HR.B_FULL // world, HR.B_SHORT: HR.B_SHORT // world}
+    names = ("flat_g", "flat[True]", "adam_m", "adam_v", "adam_vmax")
+
+    def make(b):
+        e = E.Engine(E.EngineConfig(**HR.engine_kwargs()), dev, max_batch=b, dtype=dtype)
+        return e, D.GradSync(e.flat_g, e.bucket_ranges(), world, force=True)
+
+    def one(e, g, fid, mult, bad, who):
+        b = per[HR.FEEDS[fid][0]]
+        h, m, c, y = [d(x[rank * b:(rank + 1) * b]) for x in HR.feed(fid)]
+        e.scaler.mult = mult
+        e.forward_indexed(comb, h, m, c, y, tabs)
+        e.backward(after_bucket=g.launch)
+        if sorted(g.pending) != list(range(len(g.ranges))):
+            bad.append("%s %s: collectives in flight behind backward: %s" % (who, fid, sorted(g.pending)))
+        e.step(lr=HR.LR, grad_scale=g.scale, sync=g)
+        if g.pending:
+            bad.append("%s %s: collectives still pending behind step(sync=): %s" % (who, fid, sorted(g.pending)))
+        torch.cuda.synchronize()
+        return [x.clone() for x in (e.flat_g, e.flat[True], e.adam_m, e.adam_v, e.adam_vmax)]
+
+    eng, gs = make(per[HR.B_FULL])
+    eng.load_state_dict(P)
+    D.broadcast_flat([eng.flat[True], eng.flat[False]])
+    eng.refresh_shadows(all_layers=True)
+    bad, moved = [], []
+    for n, (fid, mult) in enumerate([("full_a", 1.0), ("short_a", 1.0), ("full_b", 1.0), ("full_a", 0.5), ("full_a", 1.0)]):
+        sd, osd = eng.state_dict(), eng.optimizer_state_dict()
+        p0 = eng.flat[True].clone()
+        got = one(eng, gs, fid, mult, bad, "long-lived")
+        fresh, fgs = make(per[HR.FEEDS[fid][0]])
+        fresh.load_state_dict(sd)
+        fresh.load_optimizer_state_dict(osd)
+        want = one(fresh, fgs, fid, mult, bad, "fresh")
+        for k, a, w in zip(names, got, want):
+            if not torch.equal(a, w):
+                bad.append("step %d (%s, mult %g): %s differs from the fresh engine's in %d elements, max |diff| %.3e" % (
+                    n + 1, fid, mult, k, int((a != w).sum()), float((a.double() - w.double()).abs().max())))
+        moved.append(not torch.equal(p0, got[1]) and bool(torch.isfinite(got[0]).all()) and float(got[0].abs().max()) > 0.0)
+        del fresh, fgs, want
+    eng.scaler.drain(eng)
+    for msg in bad:
+        print("HISTORY MISMATCH rank %d: %s" % (rank, msg))
+    np.savez(out_path % rank, params=eng.flat[True].cpu().numpy(), skipped=np.int64(eng.scaler.skipped), steps=np.int64(eng.step_count),
+             mismatches=np.int64(len(bad)), messages=np.asarray(bad, dtype=str), moved=np.asarray(moved), mult=np.float64(eng.scaler.mult))
+    D.barrier()
+    if torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 6:                   # stage 2 with options (the module docstring's argument list, then a JSON object)
+    if len(sys.argv) > 5 and sys.argv[5] == "history":
+        run_history(sys.argv[1], sys.argv[2])
+    elif len(sys.argv) > 6:                   # stage 2 with options (the module docstring's argument list, then a JSON object)
         import json
         assert sys.argv[5] == "stage2"
         run(sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), json.loads(sys.argv[6]))

@@ -763,8 +763,8 @@ class Engine:
     group_sgemm = True   # False: the independent fp32 GEMMs of the heads one tnr_sgemm each (_sgemm_group; `AB=group_sgemm:0:1 tools/step_ab.py`)
     fused_user_fwd = True    # False: fc1 of the user encoders as fp32 GEMMs in front of tnr_user_score_fwd, four launches more per pass (EXPERIMENTS.md, tools/scratch/uf_time.py)
     teacher_stream = None    # a torch.cuda.Stream: the teacher side of the forward on it; no gain measured (`AB=teacher_stream:0:1 tools/step_ab.py`)
-    fcache = None        # build_frozen_cache(): (hidden states entering layer lo, additive masks, the table's address, its rows) per news
-    _pos_cache = None    # _pos_ids(): (key, position ids) of the resident token table
+    fcache = None        # build_frozen_cache(): (hidden states entering layer lo, additive masks, the table's _table_key, its rows, the table)
+    _pos_cache = None    # _pos_ids(): (_table_key, position ids, the table) of the resident token table
     _red_ginv = None     # _red_check(): the 1 / (loss scale) the recorded reduction tables carry
     dyprem = dh1prem = None  # set_dropout(): the masked LayerNorm-backward outputs, allocated by the first call that turns dropout on
     nr_s = nr_t = None   # _alloc_workspace() under nrms_heads: the student's / teachers' (blended rows, q|k|v, [ctx | candidates])
@@ -879,7 +879,11 @@ class Engine:
         news table their output is a function of the news id alone: compute it ONCE for every row -- hidden states
         entering layer `lo` (n+1, L*H) 16-bit, 2.4 GB for 51 k titles, plus the additive masks -- and let encode() gather
         rows instead of re-running the embedding and the frozen layers every step.  Bit-identical to recomputing
-        (rows are processed independently); the reference recomputes, bench.py's headline does too."""
+        (rows are processed independently); the reference recomputes, bench.py's headline does too.
+        The entry is for THIS table as it is now: it keeps the table tensor (its address cannot be handed out again while the
+        entry lives) and its _table_key - address, shape, dtype and torch's version counter - and encode() takes the cache only
+        for a table with that key.  A table rewritten in place through torch (copy_), another table, a view with fewer rows:
+        a miss, which recomputes like any foreign table; call this again to cache the new contents."""
         self.fcache = None
         if self.lo == 0:
             return False
@@ -893,13 +897,23 @@ class Engine:
             x = self.encode(news_combined, cnt, nidx=idx, stop_at=self.lo, train=False)
             fx[s0:s0 + cnt].copy_(x[:cnt * L].view(cnt, L * H))
             fm[s0:s0 + cnt].copy_(self.mask_add[:cnt])
-        self.fcache = (fx.view(torch.float32), fm, news_combined.data_ptr(), n)
+        self.fcache = (fx.view(torch.float32), fm, self._table_key(news_combined), n, news_combined)
         return True
+
+    @staticmethod
+    def _table_key(tok):
+        """What an entry cached for a resident table is valid for: (address, shape, dtype, version counter).  torch counts every
+        in-place write it makes to the storage (a view shares its base's counter), so a table refreshed by copy_ is another key;
+        whoever caches under it keeps `tok` itself beside the entry, so that no other table can get the address.  A kernel that
+        writes the table through its raw pointer is not counted - rebuild the caches after one."""
+        return (tok.data_ptr(), tuple(tok.shape), tok.dtype, tok._version)
 
     def _pos_ids(self, tok):
         """RoBERTa position ids of a token table (rows [ids | mask], any integer dtype) -> (rows, L) int32; the resident table's
-        are computed once (cached by its address).  Integer index preparation, like the torch.cat of the news indices."""
-        key = (tok.data_ptr(), tuple(tok.shape))
+        are computed once and served again for a table with the same _table_key (a view of the whole unchanged table hits; one
+        with fewer rows, the table rewritten in place, or another table at an address that was free again does not: the entry
+        keeps the table tensor).  Integer index preparation, like the torch.cat of the news indices."""
+        key = self._table_key(tok)
         c = self._pos_cache
         if c is not None and c[0] == key:
             return c[1]
@@ -907,7 +921,7 @@ class Engine:
         ne = (tok[:, :L] != pad)
         pid = (torch.cumsum(ne.to(torch.int32), 1) * ne + pad).to(torch.int32).contiguous()
         if tok.shape[0] > 4 * self.N_alloc:          # a resident table, not a per-step batch
-            self._pos_cache = (key, pid)
+            self._pos_cache = (key, pid, tok)
         return pid
 
     # encode() and backward_encoder_steps() work on a list of PARTS laid one behind the other in this engine's per-token buffers:
@@ -996,7 +1010,7 @@ class Engine:
         fc = self.fcache if self.drop_cur is None else None   # a cached prefix has no fresh masks
         assert not s.two or (fc is None and stop_at is None and out is None and not extra and cfg.pooling == "att")
         first = 0
-        if fc is not None and nidx is not None and stop_at is None and tok.data_ptr() == fc[2]:
+        if fc is not None and nidx is not None and stop_at is None and self._table_key(tok) == fc[2]:
             # frozen prefix from the per-news cache (build_frozen_cache): two row gathers replace embedding + lo layers
             T.call("tnr_gather_rows", fc[0], fc[3], nidx, n_seq, fc[0].shape[1], 1, self.x0.view(torch.float32), n_seq, 0)
             T.call("tnr_gather_rows", fc[1], fc[3], nidx, n_seq, self.Lr, 1, self.mask_add, n_seq, 0)

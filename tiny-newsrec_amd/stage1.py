@@ -210,8 +210,11 @@ class Stage1Engine:
         if not ok and self._joint_rows_written:
             # a per-pass step after joint ones (a tools/ A/B, `joint` switched off): the title engine's own kernels rely on ZERO rows
             # behind its N Lt rows (the weight gradient reads up to the next multiple of 64), where the joint passes have put body
-            # rows - lay the title workspace out afresh, once
+            # rows - lay the title workspace out afresh, once.  The body engine's recorded reduction tables go with it: its backward
+            # reads its rows of dvec from the TITLE engine's dS (backward: dS[N:Rt]), so a table recorded by an earlier per-pass step
+            # carries the address of the buffer that was just replaced
             t._alloc_workspace(t.B_alloc)
+            b.red.clear()
         self._joint_rows_written = ok
         return ok
 
