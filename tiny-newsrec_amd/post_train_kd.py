@@ -187,7 +187,9 @@ def train(args):
     from stage1 import Stage1Engine
     size, rank, local = utils.init_hvd_cuda(args.enable_hvd, True)
     dev = "cuda:%d" % local
-    random.seed(args.seed + rank)
+    # the negatives' generator is this process's own: the stream random.seed(args.seed + rank) stands for, whatever draws from the
+    # global generator in between (the first import of transformers in a process does)
+    rng = random.Random(args.seed + rank)
     if args.synthetic:
         import hashinit
         import synth
@@ -251,10 +253,13 @@ def train(args):
         order = order[rank::size]
         per_rank = (n_docs // size) // B                        # the same on every rank (len(order) differs by one across ranks)
         steps = per_rank if not args.max_steps else min(args.max_steps, per_rank)
+        if per_rank == 0:
+            logging.warning("[%d] %d documents on %d rank(s) are fewer than one batch of %d each: no step is taken, the checkpoint "
+                            "will hold the untrained weights", rank, n_docs, size, B)
         sums = torch.zeros(5, device=dev)                                          # loss, target, distill, emb, acc
         t0 = time.time()
         for cnt in range(1, steps + 1):
-            idx_h = sample_indices(random, order[(cnt - 1) * B:cnt * B], n_docs, args.npratio)
+            idx_h = sample_indices(rng, order[(cnt - 1) * B:cnt * B], n_docs, args.npratio)
             idx = torch.from_numpy(idx_h).to(dev)
             body_idx = torch.from_numpy(np.ascontiguousarray(idx_h[:, 0])).to(dev) if idx_h.dtype == np.int32 else None
             losses, score = eng.forward_indexed(d_title, d_body, idx, label, d_tt, d_tb, body_idx=body_idx)
