@@ -778,6 +778,38 @@ int tnr_rank_metrics(const float* users, int64_t u_rs, int64_t B, const float* n
                      int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * In-batch negatives of the target loss (csrc/inbatch.hip; no counterpart in the reference, whose target term is a softmax over
+ * an impression's own C = 1 + npratio candidates).  A batch of B impressions has M = B * C candidate slots; slot j = b' * C + c'
+ * holds news id cand_ids[b', c'].  Foreign slot j is a negative of impression b - bit E[b, j] - iff
+ *   1. b' != b;   2. its id is not 0 (the padding news);   3. no earlier slot j' < j holds the same id (a distinct news counts
+ *   once per batch, at its first slot: this bit depends on j alone);   4. its id is not among cand_ids[b, :] (so never b's own
+ *   positive);   5. its id is not among hist_ids[b, :] (all U entries, whatever the history mask says).
+ * target_b = -log softmax(score[b, 0:C] U {z[b, j] : E[b, j]})[label_b] at temperature 1, z[b, j] = the fp32 fma chain over
+ * k = 0, 1, ..., D - 1 from +0 of users[b, k] * cands[j, k]: tnr_topk_scores' and tnr_rank_metrics' bits for the same pair, which
+ * depend on (user row, candidate row, D) alone.  E = 0 everywhere (B = 1, say) is the plain target loss.
+ * tnr_inbatch_plan: ids int32 (B, U) / (B, C) -> elig (B, W) uint32 words, W = ceil(M / 32), bit j of row b = E[b, j], bits at and
+ *   above M zero; count[b] int32 = the bits set in row b; first_ws: W words of workspace (rule 3's bit per slot).  Two launches.
+ * tnr_inbatch_loss: users (B rows, stride u_rs), cands (M rows, stride c_rs), score (B, C), label int64 (B).  ADDS
+ *   coef * (p - onehot) / B into dscore[b, :], writes the whole row dz[b, :] = coef * p_j / B (0 where E = 0) of dz (B, M), z[b, j]
+ *   for eligible j only (z (B, M) or NULL), per[b] = target_b, and losses[1] = mean_b target_b (summed in a fixed order by a
+ *   second, one-workgroup launch); the other losses are not touched.  The row of a slot with E[b, j] = 0 is not read for b.
+ *   The sum of exponentials runs in a fixed order by RANK among the impression's eligible slots (own candidates first), and its
+ *   log is taken as log1p(sum - 1): bit-identical from run to run, an impression's values do not depend on its place in the
+ *   batch, and a loss of 1e-6 (a dominating positive) keeps its digits.  Limits: C <= 16, B * C <= 8192, D <= 1024, D % 4 == 0, strides >= D (16-byte aligned operands with strides % 4
+ *   == 0 take 16-byte loads, others scalar ones).
+ * tnr_inbatch_bwd: one launch; duser (B, D) [b] += sum over set bits j ascending of dz[b, j] cands[j], dcand (M, D) [j] += sum over
+ *   b ascending with bit j set of dz[b, j] users[b].  Every row has one owner; a row without a set bit is not touched.
+ * No float atomics, no allocation, no host synchronisation.  Anything outside the limits or a null required pointer launches
+ * nothing, writes nothing and returns TNR_EINVAL with the limit named in tnr_last_error(). */
+int tnr_inbatch_plan(const int32_t* hist_ids, const int32_t* cand_ids, uint32_t* elig, int32_t* count, uint32_t* first_ws, int B,
+                     int U, int C, void* stream);
+int tnr_inbatch_loss(const float* users, int64_t u_rs, const float* cands, int64_t c_rs, const float* score, const int64_t* label,
+                     const uint32_t* elig, float coef, float* dscore, float* dz, float* z, float* per, float* losses, int B, int C,
+                     int D, void* stream);
+int tnr_inbatch_bwd(const float* dz, const uint32_t* elig, const float* users, int64_t u_rs, const float* cands, int64_t c_rs,
+                    float* duser, float* dcand, int B, int C, int D, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Collectives of the data-parallel step.  Replace hvd.init / hvd.broadcast_parameters /
  * hvd.broadcast_optimizer_state (Tiny-NewsRec/run.py:141-144, utils.py:43-60) and the gradient all-reduce inside
  * hvd.DistributedOptimizer (run.py:145-149: average of the trainable parameters' gradients, fp32, no compression).

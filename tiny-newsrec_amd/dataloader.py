@@ -29,7 +29,8 @@ class IndexBatch(tuple):
 
 class RowBatch(tuple):
     """The reference's 6-tuple (dataloader.py:172); from the producer thread its tensors came over in one staged copy (ready =
-    its event).  plan: the batch's de-duplication plan (dedup.py) under --dedup_news, else None."""
+    its event).  plan: the batch's de-duplication plan (dedup.py) under --dedup_news, else None.  ids: (hist_idx (B, U), cand_idx
+    (B, C)) int32, the news indices the token rows were gathered with, under --inbatch_negatives, else None."""
 
 
 class DataLoaderTrain:
@@ -45,6 +46,7 @@ class DataLoaderTrain:
         self.teacher_embs, self.news_combined, self.news_index = teacher_embs, news_combined, news_index
         self.resident = enable_gpu if resident is None else resident
         self.dedup = bool(getattr(args, "dedup_news", False))
+        self.inbatch = bool(getattr(args, "inbatch_negatives", False))
         self.decode_process = bool(getattr(args, "decode_process", False)) and enable_prefetch
         self.epoch = -1
         self.sampler = None
@@ -102,22 +104,29 @@ class DataLoaderTrain:
         if self.dedup:
             from dedup import build_plan
             plan = build_plan(h, c)
+        # --inbatch_negatives: the token rows carry no news ids, so the decoded h, c ride on the batch as `.ids`, the way `.plan` does
+        ids = (t(np.ascontiguousarray(h, np.int32)), t(np.ascontiguousarray(c, np.int32))) if self.inbatch else None
         if self.enable_gpu and self.enable_prefetch and threading.current_thread() is self._thread:
-            return self._rows_to_device(out, plan)              # producer thread: one staged copy on its own stream
+            return self._rows_to_device(out, plan, ids)         # producer thread: one staged copy on its own stream
         if self.enable_gpu:
             out = [x.cuda() if isinstance(x, torch.Tensor) else [v.cuda() for v in x] for x in out]
             plan = plan.to("cuda") if plan is not None else None
+            ids = tuple(x.cuda() for x in ids) if ids is not None else None
         res = RowBatch(out)
         res.plan = plan
+        res.ids = ids
         return res
 
-    def _rows_to_device(self, out, plan=None):
+    def _rows_to_device(self, out, plan=None, ids=None):
         """Reference mode from the producer thread: the reference's 4 + 2 T `.cuda()` calls (dataloader.py:160-170) are pageable copies
         on the default stream - 8.1 MB per step that queue between the training thread's kernels (+0.8 ms on a 7.6 ms step).  Here the
         same tensors leave as ONE pinned staging buffer and ONE asynchronous copy on the producer's own stream; the consumer's stream
         waits for its event (__next__).  Same 6-tuple, same values."""
         dev = torch.device("cuda", self.cuda_device_idx)
         flat = [out[0], out[1], out[2], out[3]] + list(out[4]) + list(out[5])
+        if ids is not None:                                     # --inbatch_negatives: the two id arrays, in the same copy
+            flat += list(ids)
+        n_ids = 2 if ids is not None else 0
         if plan is not None:                                    # the de-duplication plan's four index arrays ride in the same copy
             flat += [torch.from_numpy(getattr(plan, k)) for k in ("uniq", "inv", "order", "seg")]
         words = [x.numpy().reshape(-1).view(np.int32) for x in flat]       # int64 parts as pairs of words
@@ -142,10 +151,11 @@ class DataLoaderTrain:
         res = RowBatch((dv[0], dv[1], dv[2], dv[3], dv[4:4 + T_], dv[4 + T_:4 + 2 * T_]))
         res.ready, res.buf = ev, d
         res.plan = None
+        res.ids = tuple(dv[4 + 2 * T_:4 + 2 * T_ + n_ids]) if n_ids else None
         if plan is not None:
             from dedup import DedupPlan
             res.plan = DedupPlan()
-            for k, v in zip(("uniq", "inv", "order", "seg"), dv[4 + 2 * T_:]):
+            for k, v in zip(("uniq", "inv", "order", "seg"), dv[4 + 2 * T_ + n_ids:]):
                 setattr(res.plan, k, v)
             res.plan.n_enc, res.plan.n_unique, res.plan.n_slots = plan.n_enc, plan.n_unique, plan.n_slots
         return res

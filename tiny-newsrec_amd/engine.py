@@ -645,6 +645,7 @@ class Engine:
         N = B * (cfg.U + cfg.C)
         Mp = _rup(N * L + self.extra_rows, 128)
         self.B_alloc, self.N_alloc, self.Mp = B, N, Mp
+        self._inbatch = None               # the in-batch-negatives buffers follow the batch (_inbatch_buffers)
         Nx = N + self.extra_seqs           # per-sequence partials / pooled vectors with room for a second pass's sequences
         if self.f16:
             # the losses are batch means, so activation gradients shrink as 1 / B: the scale grows with the batch in powers of two
@@ -762,6 +763,8 @@ class Engine:
     sg_kdiv = 256        # K per split of the small fp32 GEMMs (_sgemm_problem; 128 was 0.3 % slower: `AB=sg_kdiv:128:256 tools/step_ab.py`)
     group_sgemm = True   # False: the independent fp32 GEMMs of the heads one tnr_sgemm each (_sgemm_group; `AB=group_sgemm:0:1 tools/step_ab.py`)
     fused_user_fwd = True    # False: fc1 of the user encoders as fp32 GEMMs in front of tnr_user_score_fwd, four launches more per pass (EXPERIMENTS.md, tools/scratch/uf_time.py)
+    _ib_on = False           # the last forward ran with in-batch negatives (forward(inbatch_ids=...)): backward adds their gradient
+    _inbatch = None          # ... and their buffers, made on first use (_inbatch_buffers)
     teacher_stream = None    # a torch.cuda.Stream: the teacher side of the forward on it; no gain measured (`AB=teacher_stream:0:1 tools/step_ab.py`)
     fcache = None        # build_frozen_cache(): (hidden states entering layer lo, additive masks, the table's _table_key, its rows, the table)
     _pos_cache = None    # _pos_ids(): (_table_key, position ids, the table) of the resident token table
@@ -1212,29 +1215,49 @@ class Engine:
                              "kernels read up to the next multiple of 64 rows and would sum an earlier pass's rows into this step's "
                              "gradients; build the plan with quantum=64 (dedup.build_plan's default)" % (plan.n_enc, L, plan.n_enc * L))
 
-    def forward_indexed(self, news_combined, hist_idx, history_mask, cand_idx, label, teacher_tables, plan=None):
+    def forward_indexed(self, news_combined, hist_idx, history_mask, cand_idx, label, teacher_tables, plan=None, inbatch=False):
         """The same step fed the way the resident-table loader feeds it: news_combined (n+1, 2L) int32 and
         teacher_tables (T, n+1, D) fp32 stay in HBM; per step only hist_idx (B,U), cand_idx (B,C) int32 news
-        indices, the mask and the labels arrive (dataloader.py:129-149 at index level)."""
+        indices, the mask and the labels arrive (dataloader.py:129-149 at index level).
+        inbatch=True: in-batch negatives in the target loss (forward's inbatch_ids), with the indices themselves as the news ids."""
         return self.forward(None, history_mask, None, label, teacher_tables=teacher_tables, t_hidx=hist_idx,
-                            t_cidx=cand_idx, news_combined=news_combined, plan=plan)
+                            t_cidx=cand_idx, news_combined=news_combined, plan=plan,
+                            inbatch_ids=(hist_idx, cand_idx) if inbatch else None)
 
     def forward(self, history, history_mask, candidate, label, teacher_hist=None, teacher_cand=None,
-                teacher_tables=None, t_hidx=None, t_cidx=None, news_combined=None, plan=None):
+                teacher_tables=None, t_hidx=None, t_cidx=None, news_combined=None, plan=None, inbatch_ids=None):
         """Model.forward model_bert.py:262-305.  Teacher embeddings either as the reference's lists of
         (B,U,D)/(B,C,D) tensors, or as resident tables (T,R,D) + int32 row ids (B,U)/(B,C).
-        Returns the device tensor [distill, target, emb, -] and student_score (B,C)."""
+        Returns the device tensor [distill, target, emb, -] and student_score (B,C).
+        inbatch_ids = (hist_ids (B,U), cand_ids (B,C)) news ids: the target loss ranks each impression's positive against the other
+        impressions' candidates as well (include/tnr_hip.h, tnr_inbatch_*: the five rules) - losses[1] is then
+        the loss over that larger set, the distillation and embedding terms and student_score are what they are without it, and
+        backward() adds the new term's gradient to the user and candidate rows.  None or False: the reference's loss, and not one
+        call or buffer more."""
         cfg = self.cfg
         B = history_mask.shape[0]
         U, C, L, D, T_ = cfg.U, cfg.C, cfg.L, cfg.D, cfg.T
         if plan is not None:
             self._check_plan(plan, B * (U + C))      # before anything is launched or re-laid
+        if inbatch_ids is None or inbatch_ids is False:
+            inbatch_ids = None
+        elif cfg.stage1:
+            raise ValueError("inbatch_ids with stage1=True: stage 1 has no users and no target loss to extend")
+        elif inbatch_ids is True or len(inbatch_ids) != 2 or tuple(inbatch_ids[0].shape) != (B, U) or tuple(inbatch_ids[1].shape) != (B, C):
+            raise ValueError("inbatch_ids must be the pair (hist_ids (B, U), cand_ids (B, C)) of news ids: token rows carry none "
+                             "(forward_indexed(inbatch=True) passes its indices)")
         self._prepare(B)
         N = B * (U + C)
         Rt = N + B
         self.cur = (B, N, Rt)
         self.mask = history_mask.to(torch.float32).contiguous()
         self.label = label.to(torch.int64).contiguous()
+        self._ib_on = inbatch_ids is not None
+        if self._ib_on:
+            # ids only: nothing of the step is needed, so it leads the step
+            ib = self._inbatch_buffers()
+            ids = [x.to(device=self.dev, dtype=torch.int32).contiguous() for x in inbatch_ids]
+            T.call("tnr_inbatch_plan", ids[0], ids[1], ib["elig"], ib["count"], ib["first_ws"], B, U, C)
         idx = None
         if news_combined is not None or teacher_tables is not None:
             if (t_hidx.dtype == torch.int32 and t_cidx.dtype == torch.int32 and t_hidx.is_contiguous() and t_cidx.is_contiguous()
@@ -1304,14 +1327,37 @@ class Engine:
                            B * D, self.score, self.e_u, self.alpha_u, self.den_u, B, C, self.nr_s)
         if T_ > 0:
             main.wait_stream(side)
-        T.call("tnr_kd_score_loss", self.score, self.t_score if T_ else None, self.label, cfg.temperature, cfg.coef,
-               self.tw if T_ else None, self.dscore, self.losses, B, C, T_)
+        T.call("tnr_kd_score_loss", self.score, self.t_score if T_ else None, self.label, cfg.temperature,
+               0.0 if self._ib_on else cfg.coef, self.tw if T_ else None, self.dscore, self.losses, B, C, T_)
+        if self._ib_on:
+            # dscore holds the distillation part alone (coef = 0 above); this adds the target part over own + eligible foreign
+            # candidates and overwrites losses[1]
+            T.call("tnr_inbatch_loss", S[N:], D, S[B * U:], D, self.score, self.label, ib["elig"], cfg.coef, self.dscore, ib["dz"],
+                   None, ib["per"], self.losses, B, C, D)
         if T_ > 0:
             T.call("tnr_kd_embed_loss", S, self.Pm, self.tw, self.losses[2:], self.dS, self.dP, self.kd_part, B, U, C, D, T_)
         else:
             self.dS[:Rt].zero_()
             self.losses[2:3].zero_()
         return self.losses, self.score[:B]
+
+    def _inbatch_buffers(self):
+        """The buffers of the in-batch negatives (forward(inbatch_ids=...)), made on first use for the batch the workspace is laid
+        out for and dropped with it (_alloc_workspace): elig (B, W) / first_ws (W) bit words, count (B) int32, dz (B, B C), per (B)."""
+        if self._inbatch is None:
+            B, M = self.B_alloc, self.B_alloc * self.cfg.C
+            W = (M + 31) // 32
+            i32 = lambda *s: torch.zeros(s, device=self.dev, dtype=torch.int32)
+            f32 = lambda *s: torch.zeros(s, device=self.dev, dtype=torch.float32)
+            self._inbatch = dict(elig=i32(B, W), count=i32(B), first_ws=i32(W), dz=f32(B, M), per=f32(B))
+        return self._inbatch
+
+    def inbatch_counts(self):
+        """count[:B] of the last forward with in-batch negatives: how many foreign slots each impression was ranked against, an
+        int32 device tensor (no synchronisation here; the caller's read-back is one)."""
+        if not self._ib_on:
+            raise RuntimeError("inbatch_counts(): the last forward ran without in-batch negatives")
+        return self._inbatch["count"][:self.cur[0]]
 
     def _user_params(self, first, nm):
         """Stacked parameter views of `nm` user encoders whose first member has prefix `first`."""
@@ -1415,6 +1461,9 @@ class Engine:
             self._transform_grads(Rt, rbh, pend)
         # scorer + user encoder
         T.call("tnr_score_bwd", S, cidx, S[N:], self.dscore, dS, dS[N:], B, C, D)
+        if self._ib_on:
+            ib = self._inbatch_buffers()
+            T.call("tnr_inbatch_bwd", ib["dz"], ib["elig"], S[N:], D, S[B * U:], D, dS[N:], dS[B * U:], B, C, D)
         ue = "student.user_encoder."
         Qu, ulm = cfg.Qu, int(cfg.user_log_mask)
         w1u = g(ue + "attn.att_fc1.weight")

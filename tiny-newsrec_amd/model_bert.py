@@ -268,18 +268,21 @@ class Model(_Shell):
         optstate.check_header(osd, self.engine.dtype)
         self.engine.load_optimizer_state_dict(optstate.rekey(osd, self._engine_key))
 
-    def forward(self, history, history_mask, candidate, label, teacher_history_embs, teacher_candidate_embs, plan=None):
-        """plan: the loader's de-duplication plan of the batch (dedup.py, RowBatch.plan) or None; the reference has no such argument."""
+    def forward(self, history, history_mask, candidate, label, teacher_history_embs, teacher_candidate_embs, plan=None,
+                inbatch_ids=None):
+        """plan: the loader's de-duplication plan of the batch (dedup.py, RowBatch.plan) or None; inbatch_ids: the batch's news ids
+        (hist_ids (B, U), cand_ids (B, C)) under --inbatch_negatives (RowBatch.ids; Engine.forward) or None.  The reference has
+        neither argument."""
         eng = self.engine
         if isinstance(history, tuple) and len(history) == 4:      # resident-mode IndexBatch
             raise TypeError("use forward_indexed for resident-mode batches")
         losses, score = eng.forward(history, history_mask, candidate, label, list(teacher_history_embs),
-                                    list(teacher_candidate_embs), plan=plan)
+                                    list(teacher_candidate_embs), plan=plan, inbatch_ids=inbatch_ids)
         return self._pack(losses, score)
 
-    def forward_indexed(self, news_combined, hist_idx, history_mask, cand_idx, label, teacher_tables, plan=None):
+    def forward_indexed(self, news_combined, hist_idx, history_mask, cand_idx, label, teacher_tables, plan=None, inbatch=False):
         losses, score = self.engine.forward_indexed(news_combined, hist_idx, history_mask, cand_idx, label, teacher_tables,
-                                                    plan)
+                                                    plan, inbatch=inbatch)
         return self._pack(losses, score)
 
     def _pack(self, losses, score):
@@ -347,13 +350,13 @@ class ModelBert(Model):
                          list(rep[0])[:8], len(rep[1]), list(rep[1])[:8])
         return rep
 
-    def forward(self, history, history_mask, candidate, label, plan=None):
-        losses, score = self.engine.forward(history, history_mask, candidate, label, plan=plan)
+    def forward(self, history, history_mask, candidate, label, plan=None, inbatch_ids=None):
+        losses, score = self.engine.forward(history, history_mask, candidate, label, plan=plan, inbatch_ids=inbatch_ids)
         total = _Backward.apply(self._anchor, self, self.engine.total_loss())
         return total, score
 
-    def forward_indexed(self, news_combined, hist_idx, history_mask, cand_idx, label, plan=None):
-        losses, score = self.engine.forward_indexed(news_combined, hist_idx, history_mask, cand_idx, label, None, plan)
+    def forward_indexed(self, news_combined, hist_idx, history_mask, cand_idx, label, plan=None, inbatch=False):
+        losses, score = self.engine.forward_indexed(news_combined, hist_idx, history_mask, cand_idx, label, None, plan, inbatch=inbatch)
         total = _Backward.apply(self._anchor, self, self.engine.total_loss())
         return total, score
 

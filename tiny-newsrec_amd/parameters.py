@@ -61,6 +61,7 @@ def _flag_table():
           ("resident_tables", _B, True, dict(help="keep news_combined / teacher tables in HBM and ship indices only")),
           ("cache_frozen_layers", _B, True, dict(help="resident mode: compute the frozen lower encoder layers once per news instead of every step (identical results)")),
           ("dedup_news", _B, True, dict(help="encode each distinct news of a batch once (with and without --resident_tables, the same plan and the same bits in both; identical losses and scores; the gradients are then summed per distinct news first, so a training run agrees with --dedup_news False to rounding, not bit for bit)")),
+          ("inbatch_negatives", _B, False, dict(help="--mode train: the target loss ranks each impression's positive against the other impressions' candidates of the batch as well as its own npratio negatives (the distillation and embedding terms keep the impression's own candidates). A foreign candidate slot counts for an impression iff (1) it belongs to another impression, (2) it is not the padding news, (3) no earlier slot of the batch holds the same news - a distinct news counts once, at its first slot -, (4) the news is not among the impression's own candidates, (5) the news is not in the impression's click history. The logged target loss (and train_loss) is then over that larger set and not comparable with a run without the flag; the mean number of such negatives per impression is logged every --log_steps. Under data parallelism each worker uses the candidates of its own batch only (no collective is added). Off = the reference's loss")),
           ("decode_process", _B, True, dict(help="resident mode: TSV decode + de-duplication plan in a child process, so that the decoder does not share the GIL with the thread that launches the kernels (identical batches)")),
           ("dtype", str, "fp16", dict(choices=["bf16", "fp16"], help="16-bit activation type of the HIP kernels (fp16 meets the 1e-3 logit / loss tolerance, bf16 does not: DESIGN.md section 2)")),
           ("allow_random_init", _B, False, dict(help="start from the construction-time initialisation when --model_name does not exist (the reference's from_pretrained raises; so does this build unless this flag or --synthetic is set)")),

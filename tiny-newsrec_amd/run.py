@@ -41,6 +41,8 @@ def _train_flags(args, world):
              "max_grad_norm", "batch_size", "dtype")
     flags = {k: getattr(args, k) for k in names}
     flags["world"] = world
+    if getattr(args, "inbatch_negatives", False):        # recorded when on, as `optimizer` is: an older checkpoint ran without it
+        flags["inbatch_negatives"] = True
     if getattr(args, "optimizer", "adam") != "adam":
         flags["optimizer"] = args.optimizer
     return flags
@@ -130,8 +132,9 @@ def train(args):
         first_epoch = int(ts["epoch"])
         if args.start_epoch not in (0, first_epoch):
             raise ValueError(f"--resume True: {ck} was written at the end of epoch {first_epoch}, --start_epoch says {args.start_epoch}")
-        mine = dict(_train_flags(args, size), optimizer=args.optimizer)
-        for k, v in dict(ts.get("flags", {}), optimizer=ts.get("flags", {}).get("optimizer", "adam")).items():
+        mine = dict(_train_flags(args, size), optimizer=args.optimizer, inbatch_negatives=bool(getattr(args, "inbatch_negatives", False)))
+        for k, v in dict(ts.get("flags", {}), optimizer=ts.get("flags", {}).get("optimizer", "adam"),
+                         inbatch_negatives=ts.get("flags", {}).get("inbatch_negatives", False)).items():
             if k in mine and mine[k] != v:
                 logging.warning(f"--resume True: --{k} is {mine[k]}, the run that wrote {ck} had {v}" if k != "world" else
                                 f"--resume True: {size} worker(s), the run that wrote {ck} had {v}")
@@ -210,6 +213,7 @@ def train(args):
             logging.info(f"Best validation AUC so far: model saved to {best_path}")
         return v
 
+    inbatch = bool(getattr(args, "inbatch_negatives", False))
     logging.info("Training...")
     for ep in range(first_epoch, args.epochs):
         loss_sum, acc_sum, t0 = torch.zeros((), device="cuda"), torch.zeros((), device="cuda"), time.time()
@@ -228,15 +232,16 @@ def train(args):
             if isinstance(batch, IndexBatch):
                 h, m, c, y, plan = batch
                 if plmnr:
-                    total, y_student = model.forward_indexed(dev_news, h, m, c, y, plan)
+                    total, y_student = model.forward_indexed(dev_news, h, m, c, y, plan, inbatch=inbatch)
                 else:
-                    total, distill, emb, target, y_student = model.forward_indexed(dev_news, h, m, c, y, dev_tab, plan)
+                    total, distill, emb, target, y_student = model.forward_indexed(dev_news, h, m, c, y, dev_tab, plan, inbatch=inbatch)
             elif plmnr:
                 h, m, c, y = batch[:4]
-                total, y_student = model(h, m, c, y, plan=getattr(batch, "plan", None))
+                total, y_student = model(h, m, c, y, plan=getattr(batch, "plan", None), inbatch_ids=batch.ids if inbatch else None)
             else:
                 h, m, c, y, th, tc = batch
-                total, distill, emb, target, y_student = model(h, m, c, y, th, tc, plan=getattr(batch, "plan", None))
+                total, distill, emb, target, y_student = model(h, m, c, y, th, tc, plan=getattr(batch, "plan", None),
+                                                               inbatch_ids=batch.ids if inbatch else None)
             loss_sum += total.detach()
             acc_sum += utils.acc(y, y_student)
             optimizer.zero_grad()
@@ -251,6 +256,9 @@ def train(args):
                     tv = sorted(t for t, _, _ in tr.values())
                     logging.info("[{}] trust ratio min {:g} / median {:g} / max {:g} over {} tensors".format(
                         rank, tv[0], tv[len(tv) // 2], tv[-1], len(tv)))
+                if inbatch:      # this step's count, read back on log steps only
+                    logging.info("[{}] in-batch negatives: {:.1f} eligible per impression (target loss over 1 + {} + those)".format(
+                        rank, eng.inbatch_counts().float().mean().item(), args.npratio))
                 logging.info("[{}] Ed: {}, train_loss: {:.5f}, acc: {:.5f}, {:.1f} impressions/s{}{}{}".format(
                     rank, cnt * args.batch_size, loss_sum.item() / d, acc_sum.item() / d,
                     size * cnt * args.batch_size / max(time.time() - t0, 1e-9),

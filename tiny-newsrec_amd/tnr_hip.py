@@ -182,6 +182,9 @@ _SIG = {
     "tnr_topk_workspace": [_L, _L, _I, _I],
     "tnr_topk_scores": [_P, _L, _L, _P, _L, _L, _L, _I, _P, _L, _I, _I, _P, _P, _I, _P, _L, _P],
     "tnr_rank_metrics": [_P, _L, _L, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _I, _P],
+    "tnr_inbatch_plan": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "tnr_inbatch_loss": [_P, _L, _P, _L, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "tnr_inbatch_bwd": [_P, _P, _P, _L, _P, _L, _P, _P, _I, _I, _I, _P],
 }
 # entry points that exist twice: bf16 (plain name) and fp16 (suffix _f16)
 TYPED = ["tnr_embed_ln_fwd", "tnr_embed_ln_fwd_indexed", "tnr_embed_ln_bwd", "tnr_embed_ln_bwd_indexed", "tnr_gemm_nt", "tnr_gemm_nt_ex", "tnr_gemm_colsum_rows", "tnr_gemm_nt_route",
