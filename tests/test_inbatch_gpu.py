@@ -129,11 +129,11 @@ def test_off_is_the_step_as_it_was(monkeypatch, dtype):
 
 # ---------------------------------------------------------------------------------------------------------------- autograd
 def _news_vectors(P, x2l, cfg):
-    """torch_port.news_encoder; under mean pooling with its att_pool standing aside while it runs (variants_ref.port_grads' way:
-    the port's own embedding block and layers, the pooling swapped for x.mean(1))."""
+    """torch_port.news_encoder; under mean / cls pooling with its att_pool standing aside while it runs (variants_ref.port_grads'
+    way: the port's own embedding block and layers, the pooling swapped for x.mean(1) / x[:, 0])."""
     if cfg["pooling"] == "att":
         return TP.news_encoder(P, x2l, cfg["n_layers"], cfg["heads"])
-    assert cfg["pooling"] == "mean"
+    assert cfg["pooling"] in ("mean", "cls")
     captured, keep = {}, TP.att_pool
     TP.att_pool = lambda x, *w, **kw: captured.setdefault("x", x)[:, 0]
     try:
@@ -143,13 +143,15 @@ def _news_vectors(P, x2l, cfg):
         TP.news_encoder(P2, x2l, cfg["n_layers"], cfg["heads"])
     finally:
         TP.att_pool = keep
-    return F.linear(captured["x"].mean(1), P[TP.PFX + "dense.weight"], P[TP.PFX + "dense.bias"])
+    x = captured["x"]
+    return F.linear(x.mean(1) if cfg["pooling"] == "mean" else x[:, 0], P[TP.PFX + "dense.weight"], P[TP.PFX + "dense.bias"])
 
 
-def port_step(model, name, teachers):
+def port_step(model, name, teachers, embed=False):
     """Model.forward (torch_port.model_forward's formulas) with the target term over own + eligible foreign candidates, and its
-    autograd gradients.  -> (losses [distill, target, emb] float64, score (B, C), {key: gradient}); computed once."""
-    key = (model, name, teachers)
+    autograd gradients.  -> (losses [distill, target, emb] float64, score (B, C), {key: gradient}); computed once.
+    embed: the five embedding parameters train as well (embed_train_ref.port_grads' way)."""
+    key = (model, name, teachers, embed)
     if key in _PORT:
         return _PORT[key]
     cfg = V.oracle_cfg(model)
@@ -157,6 +159,10 @@ def port_step(model, name, teachers):
     if not teachers:
         Pn = {k: v for k, v in Pn.items() if not k.startswith(("teachers.", "transform_matrix."))}
     P = TP.make_params(Pn, cfg["trainable_layers"])
+    if embed:
+        from embed_train_ref import EMB_KEYS
+        for k in EMB_KEYS:
+            P[k].requires_grad_(True)
     h, c, m, y = R.engine_feed(name)
     El = torch.from_numpy(R.eligibility(h, c).astype(bool))
     h, c = torch.from_numpy(h.astype(np.int64)), torch.from_numpy(c.astype(np.int64))
@@ -192,23 +198,39 @@ def port_step(model, name, teachers):
         emb = (torch.stack(NE, -1) * tw).sum(-1).mean() + (torch.stack(UE, -1) * tw).sum(-1).mean()
     (distill + cfg["coef"] * target + emb).backward()
     G = {k: (v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape), np.float32)) for k, v in P.items() if v.requires_grad}
+    if embed:                                     # nn.Embedding(padding_idx=0): the padding row has no gradient (embed_train_ref.py)
+        G[EMB_KEYS[0]] = G[EMB_KEYS[0]].copy()
+        G[EMB_KEYS[0]][0] = 0.0
     _PORT[key] = (np.array([float(distill.detach()), float(target.detach()), float(emb.detach())], np.float64), score.detach().numpy(), G)
     return _PORT[key]
 
 
-def against_port(dtype, model, name, teachers):
-    ref_l, ref_s, G = port_step(model, name, teachers)
+def against_port(dtype, model, name, teachers, mult=1.0, embed_gtol=None):
+    """mult: the fp16 scaler's multiplier the step runs at.  embed_gtol: train_embeddings=True, the five embedding keys held to
+    this bound (tests/test_embed_train_gpu.py's), every other key to widths_ref.TOLS as ever."""
+    embed = embed_gtol is not None
+    ref_l, ref_s, G = port_step(model, name, teachers, embed)
     ltol, stol, gtol = W.TOLS[dtype]
     B = ref_s.shape[0]
-    eng = make(dtype, B, model, teachers)
+    more = dict(train_embeddings=True) if embed else {}
+    eng = make(dtype, B, model, teachers, **more)
+    assert mult == 1.0 or eng.f16
+    eng.scaler.mult = mult
     got = run(eng, name, True, model=model)
-    off = run(make(dtype, B, model, teachers), name, False, model=model, backward=False)
+    off = run(make(dtype, B, model, teachers, **more), name, False, model=model, backward=False)
     torch.cuda.synchronize()
     assert torch.equal(got["score"], off["score"]), "student_score moved with the option"
     assert (got["count"].cpu().numpy() == R.eligibility(*R.fixture(name)).sum(1)).all()
     le = np.abs(got["losses"][:3].cpu().numpy() - ref_l).max() / max(1.0, np.abs(ref_l).max())
     se = np.abs(got["score"].cpu().numpy() - ref_s).max() / max(1.0, np.abs(ref_s).max())
-    worst, wk, bad = V.compare_grads(model, list(eng.grads), lambda k: eng.grad(k).cpu().numpy(), G, gtol)
+    emb = []
+    if embed:
+        from embed_train_ref import EMB_KEYS as emb
+        assert set(emb) <= set(eng.grads) and set(emb) <= set(G)
+        ew, ek, ebad = V.compare_grads(model, list(emb), lambda k: eng.grad(k).cpu().numpy(), G, embed_gtol)
+        print("\n[inbatch %s %s %s] worst embedding gradient %.2e of %.2e (%s)" % (model, name, dtype, ew, embed_gtol, ek[-48:]))
+        assert not ebad and np.isfinite(ew), ebad
+    worst, wk, bad = V.compare_grads(model, [k for k in eng.grads if k not in emb], lambda k: eng.grad(k).cpu().numpy(), G, gtol)
     print("\n[inbatch %s %s %s teachers %s] loss %.2e score %.2e worst gradient %.2e (%s); target %.4f (plain %.4f)" % (
         model, name, dtype, teachers, le, se, worst, wk[-48:], ref_l[1], float(off["losses"][1])))
     assert le < ltol and se < stol

@@ -79,6 +79,86 @@ def test_hand_worked_example():
     assert (R.words(E2) == np.array([[0x80000000, 1]], np.uint32)).all()
 
 
+# ------------------------------------------------------------------------------------- the vectorised forms and the limit fixtures
+@pytest.mark.parametrize("name", R.FIXTURES)
+def test_vectorised_forms_equal_the_loops(name):
+    """eligibility_v / words_v exactly (every stage), loss_v / bwd_v to 1e-12 of the loops, on every fixture the loops can do;
+    NaN in the rows nobody is eligible for must not reach the vectorised results (the loops never read those rows)."""
+    hist, cand = R.fixture(name)
+    st, sv = R.eligibility(hist, cand, stages=True), R.eligibility_v(hist, cand, stages=True)
+    assert all(a.dtype == b.dtype and (a == b).all() for a, b in zip(st, sv))
+    E = st[4]
+    assert (R.eligibility_v(hist, cand) == E).all()
+    wl, wv = R.words(E), R.words_v(E)
+    assert wl.dtype == wv.dtype == np.uint32 and wl.shape == wv.shape and (wl == wv).all()
+    for coef, scale in ((0.2, 1.0), (1.0, 30.0)):
+        users, cands, score, label, _ = _inputs(name, 12, 5, scale)
+        dead = cands.copy()
+        dead[E.sum(0) == 0] = np.nan
+        a, b = R.loss(users, cands, score, label, E, coef), R.loss_v(users, dead, score, label, E, coef)
+        assert abs(a["target"] - b["target"]) <= 1e-12 * abs(a["target"])
+        for k in ("per", "dscore_add", "dz"):
+            np.testing.assert_allclose(b[k], a[k], rtol=1e-12, atol=1e-300, err_msg=k)
+        _, mag = R.logits(users, cands)
+        assert (np.abs(a["z"] - b["z"]) <= 1e-12 * mag).all() and (b["z"][E == 0] == 0).all()
+        du, dc = R.bwd(a["dz"], users, cands)
+        dv, dcv = R.bwd_v(a["dz"], users, dead)
+        mu, mc = np.abs(a["dz"]) @ np.abs(cands), np.abs(a["dz"]).T @ np.abs(users)
+        assert (np.abs(du - dv) <= 1e-12 * mu).all() and (np.abs(dc - dcv) <= 1e-12 * mc).all()
+        assert np.isfinite(dv).all() and np.isfinite(dcv).all()
+
+
+def test_vectorised_loss_with_a_label_out_of_range():
+    """The kernel's convention: that impression's loss and the mean are NaN, everything else is as with a valid label."""
+    users, cands, score, label, E = _inputs("b5", 8, 4)
+    good = R.loss_v(users, cands, score, label, E, 1.0)
+    for y in (-1, 2, 200):
+        lab = label.copy()
+        lab[2] = y
+        bad = R.loss_v(users, cands, score, lab, E, 1.0)
+        others = np.arange(5) != 2
+        assert np.isnan(bad["per"][2]) and np.isnan(bad["target"]) and (bad["per"][others] == good["per"][others]).all()
+        assert (bad["dz"] == good["dz"]).all() and (bad["dscore_add"][others] == good["dscore_add"][others]).all()
+        assert np.isfinite(bad["dscore_add"]).all() and (bad["dscore_add"][2] > 0).all()
+
+
+@pytest.mark.parametrize("name", R.LIMIT_FIXTURES)
+def test_limit_fixtures_are_what_the_table_says(name):
+    """Slots, eligible slots per impression, and what each fixture exists for - asserted on the inputs, so that a fixture that
+    slid off its edge fails here and not silently."""
+    B, C, _, _, per = R.LIMITS[name]
+    for U in ((R.MAX_MIXED_U,) if name == "max_mixed" else (1, 3) if name == "w8191" else (1, 3, 50)):
+        hist, cand = R.limit_fixture(name, U)
+        assert hist.shape == (B, U) and cand.shape == (B, C) and hist.dtype == cand.dtype == np.int32
+        assert hist.min() >= 0 and cand.min() >= 0 and B * C == R.LIMIT_SLOTS[name] <= 8192 and C <= 16
+        assert R.limit_fixture(name, U)[1] is cand                                       # built once
+        st = R.eligibility_v(hist, cand, stages=True)
+        E = st[4]
+        if per is not None:
+            assert (E.sum(1) == per).all() and per == (B - 1) * C
+        elif name != "max_mixed":
+            removed = [bool((st[r - 1] > st[r]).any()) for r in range(1, 5)]
+            assert all(removed[1:]), (name, U, removed)                                  # rules 3 - 5 all fire
+            assert E.sum(1).max() > 0 and np.unique(E.sum(1)).size > 1
+    if name == "max":
+        assert ((R.words_v(E) == 0xFFFFFFFF).sum(1) == 255).all()                       # all 256 words in use: one's own is half set
+    if name == "max_mixed":
+        cond = R.max_mixed_conditions(E)
+        assert all(cond.values()), cond
+        removed = [bool((st[r - 1] > st[r]).any()) for r in range(1, 5)]
+        assert all(removed), removed
+        assert (st[2][:, 32:64].sum(0) == 511).all() and not st[1][:, 64:96].any()
+    if name == "w8191":
+        assert R.words_v(E).shape == (8191, 256) and not (R.words_v(E)[:, 255] >> np.uint32(31)).any()
+
+
+def test_the_rank_rounds_of_the_limit_fixtures():
+    """ib_loss_kernel's `for (r = tid; r < n_elig; r += 256)`: 255, 256, 257 ranks; 8176 = 31 full rounds and one of 240."""
+    got = {n: int(R.limit_eligibility(n).sum(1).max()) for n in ("r255", "r256", "r257", "max")}
+    assert got == {"r255": 255, "r256": 256, "r257": 257, "max": 8176}
+    assert R.limit_eligibility("r255") is R.limit_eligibility("r255")
+
+
 @pytest.mark.parametrize("name", R.FIXTURES)
 def test_fixture_condition(name):
     """Every id fixture of tests/test_inbatch_kernels_gpu.py and tests/test_inbatch_gpu.py (the shapes that are degenerate by

@@ -8,7 +8,8 @@ bucketed all-reduce launched from the backward's after_bucket hook exactly as ru
 mode "stage1": the same for post_train_kd.py's step (Stage1Engine: title pass writes the gradients, body pass accumulates and
 fires the buckets).
 mode "history": one long-lived Engine and one long-lived GradSync per rank through unlike steps of tests/history_ref.py, every
-step against a fresh Engine + GradSync over the same process group (run_history)."""
+step against a fresh Engine + GradSync over the same process group (run_history).
+mode "inbatch": two steps with in-batch negatives on, each rank on a half of its own (run_inbatch)."""
 import os
 import sys
 
@@ -217,8 +218,58 @@ def run_history(out_path, dtype):
         torch.distributed.destroy_process_group()
 
 
+def run_inbatch(out_path, dtype):
+    """In-batch negatives at two real ranks (tests/test_inbatch_steps_gpu.py): variants_ref's "att" model, rank 0 on
+    inbatch_ref.engine_feed("e5"), rank 1 on "e5b" - unlike halves, five impressions each.  By design a rank ranks against its
+    own batch only, so no collective is added and the reduced gradient is the sum of the two halves' own gradients.  Two steps
+    with the option on, gs.launch the hook: behind the first backward the rank waits and dumps the reduced flat_g (times the
+    scale) and its eligible counts, then steps; the second goes bucket by bucket through step(sync=gs)."""
+    sys.path.insert(0, ROOT)                # variants_ref imports the oracle package
+    import dist as D
+    import engine as E
+    import history_ref as HR
+    import inbatch_ref as R
+    import variants_ref as V
+    world, rank, _ = D.init("gloo")
+    assert world == 2
+    dev = "cuda:0"
+    torch.cuda.set_device(0)
+    d = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    eng = E.Engine(E.EngineConfig(**V.engine_kwargs("att")), dev, max_batch=5, dtype=dtype)
+    eng.load_state_dict({k: d(v) for k, v in V.weights("att").items()})
+    D.broadcast_flat([eng.flat[True], eng.flat[False]])
+    eng.refresh_shadows(all_layers=True)
+    gs = D.GradSync(eng.flat_g, eng.bucket_ranges(), world, force=True)
+    comb, tabs = d(HR.news()), d(HR.teachers())
+    h, c, m, y = [d(x) for x in R.engine_feed(("e5", "e5b")[rank])]
+    grads, counts, losses = [], [], []
+    for st in range(2):
+        ls, _ = eng.forward_indexed(comb, h, m, c, y, tabs, inbatch=True)
+        losses.append(ls.cpu().numpy().copy())
+        counts.append(eng.inbatch_counts().cpu().numpy().copy())
+        eng.backward(after_bucket=gs.launch)
+        assert sorted(gs.pending) == list(range(len(gs.ranges)))
+        if st == 0:
+            gs.wait()
+            grads.append((eng.flat_g * gs.scale).cpu().numpy().copy())
+            eng.step(lr=1e-4, grad_scale=gs.scale)
+        else:
+            eng.step(lr=1e-4, grad_scale=gs.scale, sync=gs)
+            assert not gs.pending
+            grads.append((eng.flat_g * gs.scale).cpu().numpy().copy())
+    eng.scaler.drain(eng)
+    torch.cuda.synchronize()
+    np.savez(out_path % rank, grads=np.stack(grads), counts=np.stack(counts), losses=np.stack(losses), params=eng.flat[True].cpu().numpy(),
+             scale=np.float64(gs.scale), skipped=np.int64(eng.scaler.skipped), steps=np.int64(eng.step_count))
+    D.barrier()
+    if torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 5 and sys.argv[5] == "history":
+    if len(sys.argv) > 5 and sys.argv[5] == "inbatch":
+        run_inbatch(sys.argv[1], sys.argv[2])
+    elif len(sys.argv) > 5 and sys.argv[5] == "history":
         run_history(sys.argv[1], sys.argv[2])
     elif len(sys.argv) > 6:                   # stage 2 with options (the module docstring's argument list, then a JSON object)
         import json

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(IB_T) void ib_loss_kernel(IbLoss g) {
     const int64_t y = g.label[b];
     // p - 1 of the positive as expm1: it cancels to nothing exactly where the positive dominates
     if (tid < C) g.dscore[b * C + tid] += g.coef * (tid == y ? expm1f(own - mx - lse) : __expf(own - mx - lse)) / fB;
-    if (tid == y) g.per[b] = (mx - own) + lse;
+    if (tid < C && tid == y) g.per[b] = (mx - own) + lse;             // (a label in [C, 256) has a thread, but no candidate)
     if (tid == 0 && (y < 0 || y >= C)) g.per[b] = __uint_as_float(0x7fc00000u);      // no such candidate: NaN, as a bad row scores
 }
 
